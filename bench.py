@@ -12,6 +12,11 @@ consecutive steps run in one k_step launch (pd_step_n, --fuse 128), --fuse 1 lau
 Multi-GPU: one process per GPU (torchrun), each rank steps its own contiguous env shard
 (env_offset = rank * N); the env batch shards with no data-path collective, so scaling is
 weak; the timed region is bracketed by barriers and the max over ranks is reported.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and
+prints the headline line.  `--full` adds everything else the line used to carry: the kernel-time
+replays and workload counts (roofline fields), the c3-descent, fresh and staggered windows, short
+c4 and c5 runs and the CPU baseline.  `--dump-outputs DIR` writes the last timed step's outputs.
 """
 import argparse
 import json
@@ -135,6 +140,26 @@ def timed_region(step_fn, steps, sync, dist=None, device="cpu", pre=None, post=N
     return wall
 
 
+DUMP_BYTES = 60 * 2 ** 20     # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(path, rank, arrays):
+    """--dump-outputs: each of `arrays` (name -> device tensor) as path/<name>.npy (rank 0; the
+    other ranks of a job add _rank<r> to the name), float64 where the tensor is, float32 otherwise
+    (flags and ids too).  An array beyond its share of DUMP_BYTES is written as a fixed sample of
+    its flattened elements (numpy default_rng(0), sorted positions): the same positions in every run."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        if a.nbytes > share:
+            k = share // a.itemsize
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), np.ascontiguousarray(a))
+
+
 def bench_sac(args, world, rank, local, dist):
     """Config c5: SAC data collection, 4096 envs per GPU (32 768 on 8 GPUs), pure throttle, RL
     reward, auto-reset.  One timed step = the reference's Actor (256x2, sampled, PyTorch-ROCm)
@@ -155,9 +180,33 @@ def bench_sac(args, world, rank, local, dist):
     for _ in range(args.warmup):
         col.step()
     r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    wall = timed_region(lambda k: col.step(), args.steps, torch.cuda.synchronize, dist, env.device,
-                        pre=r0.record, post=r1.record)
+    last = [None]
+
+    def one(k):
+        last[0] = col.step()
+    wall = timed_region(one, args.steps, torch.cuda.synchronize, dist, env.device, pre=r0.record, post=r1.record)
     region_ms = r0.elapsed_time(r1) / args.steps
+    if args.dump_outputs and last[0] is not None:
+        # the last timed step's transition rows (state | action | reward | next_state | done), as
+        # SACCollector.step returned them
+        dump_outputs(args.dump_outputs, rank, {"transition_rows": last[0]})
+    head = {
+        "metric": ("SAC collection env-steps/sec (c5: actor + env + RCCL all_gather of the transition rows + "
+                   "prioritized replay buffer)" if dist else
+                   "SAC collection env-steps/sec (c5: actor + env + prioritized replay buffer, one launch per step; "
+                   "one process, no collective)"),
+        "value": whole_job_rate(n, world, args.steps, wall), "unit": "env-steps/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.precision,
+        "data": "synthetic (random-init SAC actor 2-256-256-1, reference initial state, no wind)",
+        "config": {"workload": "c5: SAC collection, landing_burn_pure_throttle, rtd_rl, auto-reset",
+                   "envs_per_gpu": n, "global_envs": n * world,
+                   "parallelism": f"env-shard x{world} + all_gather" if dist else "one process (no process group)"},
+        "replay_buffer_size": len(buf) if buf is not None else None, "hip_graph": args.graph == 1,
+    }
+    if not args.full:       # the plain run: the timed steps and their line, nothing more
+        return head if rank == 0 else None
     # the dominant kernel's device time.  Eager (the default): the timed region's own event pair
     # on the stream the k_step<SAC> launches run on, per step -- the launches run back to back
     # there (rocprofv3: no gap between them), so this is their average duration with the miss
@@ -191,19 +240,7 @@ def bench_sac(args, world, rank, local, dist):
         + 4.0 * n_par / n
     fpe = 2.0 * (S * H + H * H + 2 * H * A)
     out = {
-        "metric": ("SAC collection env-steps/sec (c5: actor + env + RCCL all_gather of the transition rows + "
-                   "prioritized replay buffer)" if dist else
-                   "SAC collection env-steps/sec (c5: actor + env + prioritized replay buffer, one launch per step; "
-                   "one process, no collective)"),
-        "value": whole_job_rate(n, world, args.steps, wall), "unit": "env-steps/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": args.precision,
-        "data": "synthetic (random-init SAC actor 2-256-256-1, reference initial state, no wind)",
-        "config": {"workload": "c5: SAC collection, landing_burn_pure_throttle, rtd_rl, auto-reset",
-                   "envs_per_gpu": n, "global_envs": n * world,
-                   "parallelism": f"env-shard x{world} + all_gather" if dist else "one process (no process group)"},
-        "replay_buffer_size": len(buf), "hip_graph": args.graph == 1,
+        **head, "replay_buffer_size": len(buf),
         "roofline": {"bound": "hbm", "achieved": bpe * n / (kern_avg * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
                      "frac": bpe * n / (kern_avg * 1e-3) / 1e9 / 8000.0,
                      "traffic": pmc_traffic("c5", n) if n == 4096 else None,
@@ -264,10 +301,29 @@ def bench_pso(args, world, rank, local, dist):
     torch.cuda.synchronize()
     tot = torch.zeros((), dtype=torch.int64, device=opt.device)
 
+    last = [None]
+
     def one(k):
-        opt.generation(args.warmup + k)
+        last[0] = opt.generation(args.warmup + k)
     # episode lengths of the timed generations (a separate evaluation pass is not timed)
     wall = timed_region(one, args.steps, torch.cuda.synchronize, dist, opt.device)
+    if args.dump_outputs and last[0] is not None:
+        # what the last timed generation returned (every particle's fitness) and left behind
+        # (the swarm's next positions)
+        dump_outputs(args.dump_outputs, rank, {"fitness": last[0], "positions": opt.x32})
+    head = {
+        "metric": "PSO particle-episodes/sec (c4: fused actor rollouts + device swarm update)",
+        "value": whole_job_rate(P, world, args.steps, wall),
+        "unit": "particle-episodes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.precision,
+        "data": "synthetic (swarm initialised U(-1.5,1.5) per parameter, nominal initial state, no wind)",
+        "config": {"workload": "c4: PSO generation, landing_burn, 372-param simple_actor fused in k_step, "
+                               "2 subswarms", "particles_per_gpu": P, "global_particles": P * world,
+                   "parallelism": f"particle-shard x{world} + subswarm-minimum all_gather"},
+    }
+    if not args.full:       # the plain run: the timed generations and their line, nothing more
+        return head if rank == 0 else None
     # the dominant kernel: the policy rollout of the swarm's current positions
     # (pd_rollout_policy_chunked: k_step<POL> launches until every episode ended), replayed with a
     # HIP event pair per rollout
@@ -292,14 +348,7 @@ def bench_pso(args, world, rank, local, dist):
     # SURVEY 8(d)) x the episode's steps, + its 372 float32 actor parameters read once
     bpp = mean_len * algorithmic_bytes(args.precision, "landing_burn", False) + 4 * 372
     out = {
-        "metric": "PSO particle-episodes/sec (c4: fused actor rollouts + device swarm update)", "value": eps,
-        "unit": "particle-episodes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": args.precision,
-        "data": "synthetic (swarm initialised U(-1.5,1.5) per parameter, nominal initial state, no wind)",
-        "config": {"workload": "c4: PSO generation, landing_burn, 372-param simple_actor fused in k_step, "
-                               "2 subswarms", "particles_per_gpu": P, "global_particles": P * world,
-                   "parallelism": f"particle-shard x{world} + subswarm-minimum all_gather"},
+        **head,
         "env_steps_per_s_est": eps * mean_len, "mean_episode_len_after": mean_len,
         "global_best_fitness": opt.gbf,
         "roofline": {"bound": "hbm", "achieved": bpp * P / (kern_avg * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
@@ -336,7 +385,7 @@ def other_workloads(args, local):
     the full lines)."""
     res = {}
     for wl, kw in (("c5", dict(steps=192, warmup=32)), ("c4", dict(steps=16, warmup=2, cpu_baseline=0))):
-        sub = argparse.Namespace(**{**vars(args), **kw, "workload": wl})
+        sub = argparse.Namespace(**{**vars(args), **kw, "workload": wl, "dump_outputs": None})
         try:
             o = (bench_pso if wl == "c4" else bench_sac)(sub, 1, 0, local, None)
             res[wl] = {k: o[k] for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "dtype")}
@@ -406,10 +455,13 @@ def workload_counts(d, n, steps, lpe):
     return out
 
 
-def run_c3(args, precision, local, rank, dist, descent=False, launch_base=0, burn=None, stagger=None):
+def run_c3(args, precision, local, rank, dist, descent=False, launch_base=0, burn=None, stagger=None, full=True,
+           dump=False):
     """One c3 (or c3-descent) measurement on this rank's handle, after the staggered prologue
     (`stagger` steps, default --stagger when there is a burn-in) and `burn` untimed steps
-    (default: c3-descent's, or --c3-burn-in).  Returns the raw timings."""
+    (default: c3-descent's, or --c3-burn-in).  Returns the raw timings.  full=False stops after
+    the timed region (no kernel-time replays, no workload counts); dump=True keeps a copy of the
+    last timed step's outputs (`last`)."""
     import torch
     import pdenv
     n = args.envs
@@ -461,8 +513,9 @@ def run_c3(args, precision, local, rank, dist, descent=False, launch_base=0, bur
     # timed region: exactly K env-steps (ceil(K / F) launches), nothing else on the stream but
     # the miss flush after each launch and one event at either end (device time of the region)
     tb = bounds(W, T)
-    blob = env.checkpoint()          # every per-env buffer at the start of the timed region
-    s0 = env.stats()
+    if full:
+        blob = env.checkpoint()          # every per-env buffer at the start of the timed region
+        s0 = env.stats()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     first_timed = launch_base + launches[0]
     timed = lambda k: chunk(*tb[k])
@@ -483,6 +536,21 @@ def run_c3(args, precision, local, rank, dist, descent=False, launch_base=0, bur
             launches[0] += 1
     wall = timed_region(timed, len(tb), torch.cuda.synchronize, dist, env.device, pre=e0.record, post=e1.record)
     dev_ms = e0.elapsed_time(e1)
+    last = None
+    if dump:
+        # the last timed step's outputs, as the caller of pd_step_n / pd_step receives them (the
+        # last row the last launch wrote), and the state they left
+        row = tb[-1][1] - tb[-1][0] - 1
+        bufs = [o[row] for o in outs] if F > 1 else [env.obs_buf, env.reward_buf, env.done_buf, env.trunc_buf,
+                                                     env.trunc_id_buf]
+        last = dict(zip(("obs", "reward", "done", "truncated", "trunc_id"), (b.clone() for b in bufs)))
+        last["state"] = env.state
+    if not full:
+        # the plain run: the timed launches and their times, nothing more
+        res = dict(wall=wall, dev_ms=dev_ms, fuse=F, n=n, burn_in=burn, stagger=stagger, descent=descent, last=last,
+                   launches_total=launches[0])
+        env.close()
+        return res
     s1 = env.stats()
     # kernel duration: the timed region's launches replayed from the checkpoint (the same
     # actions and per-env state; the aero tables keep what the timed region inserted, so the
@@ -527,6 +595,7 @@ def run_c3(args, precision, local, rank, dist, descent=False, launch_base=0, bur
                              "replays": KERNEL_REPLAYS},
                nan_events=s3["nan_events"], descent=descent)
     res["launches_total"] = launches[0]   # (every launch of this handle: the replays included)
+    res["last"] = last
     env.close()
     return res
 
@@ -660,6 +729,17 @@ def main():
                     help="c3: also measure the fresh-episode window (no burn-in), reported as c3_fresh")
     ap.add_argument("--others", type=int, default=1,
                     help="c3 at one GPU: also run short c4 and c5 measurements (summarised in the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the kernel-time replays and workload "
+                         "counts behind the roofline fields, the c3-descent / c3_fresh / c3_staggered windows, the "
+                         "short c4 and c5 runs, the other precision (--secondary 1) and the CPU baseline.  Without "
+                         "it (the default) the run sets up, warms up, times --steps steps and prints the line; "
+                         "--descent, --fresh, --staggered, --others, --secondary and --cpu-baseline then select "
+                         "nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / "
+                         "float64; c3, c2: obs, reward, done, truncated, trunc_id and the state of every env; c4: fitness "
+                         "and positions; c5: the transition rows); the inputs are seeded, the same in every run")
     args = ap.parse_args()
     if args.workload == "c2":
         args.no_wind = True
@@ -697,8 +777,15 @@ def main():
         return
 
     descent_main = args.workload == "c3-descent"
-    main_res = run_c3(args, args.precision, local, rank, dist, descent=descent_main)
+    main_res = run_c3(args, args.precision, local, rank, dist, descent=descent_main, full=args.full,
+                      dump=bool(args.dump_outputs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, main_res.pop("last"))
     base = main_res["launches_total"]
+    if not args.full:
+        # the plain run measures the headline window alone: every other window below, the
+        # kernel-time replays, the counts and the CPU baseline are --full's
+        args.descent = args.fresh = args.staggered = args.secondary = args.others = args.cpu_baseline = 0
     desc = None
     if args.workload == "c3" and args.descent:
         desc = run_c3(args, args.precision, local, rank, dist, descent=True, launch_base=base)
@@ -725,7 +812,12 @@ def main():
         pmc = load_pmc("pmc_traffic.json")          # the committed PMC passes of the c3 workload
     elif descent_main:
         pmc = load_pmc("pmc_c3_descent.json")
-    summ = c3_summary(args, main_res, world, args.precision, pmc)
+    if args.full:
+        summ = c3_summary(args, main_res, world, args.precision, pmc)
+    else:
+        summ = {"value": whole_job_rate(main_res["n"], world, args.steps, main_res["wall"]),
+                "ms_per_step": main_res["wall"] / args.steps * 1e3,
+                "device_ms_per_step": main_res["dev_ms"] / args.steps}
     wl = {"c3": "c3: 65536 envs/GPU, landing_burn_pure_throttle, rtd_rl reward, wind (percentile profile drawn "
                 "per reset + VK gusts below 15 km) + tilt, auto-reset, uniform random actions" +
                 ((f"; timed after {args.stagger} staggered-start steps" if args.stagger > 0 else "; synchronized starts") +
@@ -760,7 +852,8 @@ def main():
                    "parallelism": f"env-shard x{world}"},
     }
     out.update({k: v for k, v in summ.items() if k not in ("value", "ms_per_step")})
-    out["rbf_table_misses"] = main_res["counts"]["rbf_misses_solved"]
+    if args.full:
+        out["rbf_table_misses"] = main_res["counts"]["rbf_misses_solved"]
     if desc is not None:
         ds = c3_summary(args, desc, world, args.precision, load_pmc("pmc_c3_descent.json"))
         ds["workload"] = (f"c3-descent: 3:1 high-throttle action mix, {DESCENT_BURN_IN} burn-in + {args.warmup} "

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Copy the rocprofv3 summaries of a GPU session (tools/gpu_session.sh, under gpurun_out/) into
+"""Copy the rocprofv3 summaries of a GPU session (tools/gpu_session.sh, under its SESSION_OUT
+folder, default session_out/) into
 profiles/ and reduce the PMC passes to per-launch figures for k_step.
 
   FETCH_SIZE, WRITE_SIZE: KiB per dispatch (rocprofv3 derived counters).  Per
@@ -14,7 +15,7 @@ import sys
 from collections import defaultdict
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(REPO, "gpurun_out")
+OUT = os.path.join(REPO, os.environ.get("SESSION_OUT", "session_out"))
 PROF = os.path.join(REPO, "profiles")
 
 

@@ -9,9 +9,9 @@ export TMPDIR=/tmp
 CASES=${CASES:-"c4_32768 c4_262144 c5"}
 for c in $CASES; do
   case $c in
-    c4_32768) args="--workload c4 --particles 32768 --steps 4 --warmup 2 --cpu-baseline 0" ;;
-    c4_262144) args="--workload c4 --particles 262144 --steps 2 --warmup 1 --cpu-baseline 0" ;;
-    c5) args="--workload c5 --steps 64 --warmup 8 --cpu-baseline 0" ;;
+    c4_32768) args="--full --workload c4 --particles 32768 --steps 4 --warmup 2 --cpu-baseline 0" ;;
+    c4_262144) args="--full --workload c4 --particles 262144 --steps 2 --warmup 1 --cpu-baseline 0" ;;
+    c5) args="--full --workload c5 --steps 64 --warmup 8 --cpu-baseline 0" ;;
   esac
   for pass in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
     pn=$(echo "$pass" | cut -d' ' -f1 | tr 'A-Z' 'a-z')

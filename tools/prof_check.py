@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Check a bench.py line against the rocprofv3 kernel trace of the same command.
+"""Check a `bench.py --full` line against the rocprofv3 kernel trace of the same command.
 
   python tools/prof_check.py <kernel_trace.csv> <bench log with the JSON line> [out.json]
 
-bench.py numbers its k_step launches per precision in issue order and reports, for the headline
+bench.py --full numbers its k_step launches per precision in issue order and reports, for the headline
 and for the nested c3-descent measurement, the index ranges of the timed launches and of their
 replay (`launch_index`).  This tool takes the k_step dispatches of that precision from the trace
 in dispatch order, averages the kernel durations over each range, and sets them beside the line's

@@ -29,10 +29,10 @@ case "${PART:-1}" in
     N=4096 WIND=0 TILT=0 LPE=$l FUSE=128 LAUNCHES=6 run c2_lpe$l 200 python tools/time_fused.py
   done ;;
 2)
-  run benchdrv 400 python bench.py --steps 20 --warmup 5
-  run bench 400 python bench.py
-  run c4 300 python bench.py --workload c4
-  run c5 300 python bench.py --workload c5
+  run benchdrv 400 python bench.py --full --steps 20 --warmup 5
+  run bench 400 python bench.py --full
+  run c4 300 python bench.py --full --workload c4
+  run c5 300 python bench.py --full --workload c5
   run plpe 300 python tools/policy_lpe_sweep.py
   STAGES="prof profdrv profc4 profc5" run profs 900 bash tools/gpu_session.sh ;;
 3)
@@ -57,12 +57,12 @@ case "${PART:-1}" in
   for d in 0 1; do for l in 2 1; do
     LPE=$l FUSE=128 LAUNCHES=6 DESCENT=$d run lpe_c3_d${d}_l$l 200 python tools/time_fused.py
   done; done
-  run benchdrv 300 python bench.py --steps 20 --warmup 5
-  run bench 400 python bench.py ;;
+  run benchdrv 300 python bench.py --full --steps 20 --warmup 5
+  run bench 400 python bench.py --full ;;
 6)
-  run c4 300 python bench.py --workload c4
-  run c5 300 python bench.py --workload c5
-  run c2 300 python bench.py --workload c2 --cpu-baseline 0
+  run c4 300 python bench.py --full --workload c4
+  run c5 300 python bench.py --full --workload c5
+  run c2 300 python bench.py --full --workload c2 --cpu-baseline 0
   run plpe 300 python tools/policy_lpe_sweep.py
   STAGES="prof profdrv profc4 profc5" run profs 700 bash tools/gpu_session.sh ;;
 7)
@@ -76,7 +76,7 @@ case "${PART:-1}" in
 8)
   # c5 in one launch (pd_step_sac_fused): its tests, the c5 line and its rocprofv3 trace
   run gpu_sac_tests 400 python -u -m pytest tests/ -m gpu -x -q --timeout 200 --timeout-method thread -k "sac"
-  run c5 300 python bench.py --workload c5
+  run c5 300 python bench.py --full --workload c5
   STAGES="profc5" run profs 300 bash tools/gpu_session.sh ;;
 9)
   # after the fault of part 8 (the SAC launcher dispatched the non-SAC kernel for pd_step_sac_fused:
@@ -88,9 +88,9 @@ case "${PART:-1}" in
     FUSE=128 LAUNCHES=6 DESCENT=$d run atm_d${d}_r$r 200 python tools/time_fused.py
     PDENV_ATM_TAB=0 FUSE=128 LAUNCHES=6 DESCENT=$d run atm0_d${d}_r$r 200 python tools/time_fused.py
   done; done
-  run c5 300 python bench.py --workload c5
-  run c2 300 python bench.py --workload c2 --cpu-baseline 0
-  run bench 400 python bench.py ;;
+  run c5 300 python bench.py --full --workload c5
+  run c2 300 python bench.py --full --workload c2 --cpu-baseline 0
+  run bench 400 python bench.py --full ;;
 10)
   # part 9: the tables made c3 / c3-descent slower (0.0330 / 0.0391 against 0.0315 / 0.0363) and
   # c2, c4, c5, f32 faster: which table, and the code-size effect (notab: built without them)
@@ -123,26 +123,26 @@ case "${PART:-1}" in
   for d in 0 1; do FUSE=128 LAUNCHES=6 DESCENT=$d run k_d$d 200 python tools/time_fused.py; done
   PREC=f32 FUSE=128 LAUNCHES=6 run k_f32 200 python tools/time_fused.py
   N=4096 WIND=0 TILT=0 FUSE=128 LAUNCHES=6 run k_c2 200 python tools/time_fused.py
-  run c4 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
-  PDENV_COMPACT_AT=0.5 run c4_at50 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
-  PDENV_COMPACT_AT=0.2 run c4_at20 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
-  PDENV_COMPACT=1 run c4_list 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
-  run c5 300 python bench.py --workload c5
-  run bench 400 python bench.py ;;
+  run c4 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+  PDENV_COMPACT_AT=0.5 run c4_at50 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+  PDENV_COMPACT_AT=0.2 run c4_at20 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+  PDENV_COMPACT=1 run c4_list 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+  run c5 300 python bench.py --full --workload c5
+  run bench 400 python bench.py --full ;;
 12)
   # the final build's measurement: the suite, smoke, the bench lines (defaults and the driver's
   # command), c4 / c5 / c2, rocprofv3 kernel traces (default, driver command, c4, c5) and the PMC
   # passes (c3, c3-descent); tools/collect_r03.py r04 reduces them into profiles/
   run gpu_tests 700 python -u -m pytest tests/ -m gpu -x -q --timeout 200 --timeout-method thread
   run smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
-  run bench 400 python bench.py
-  run benchdrv 300 python bench.py --steps 20 --warmup 5
-  run c4 300 python bench.py --workload c4
+  run bench 400 python bench.py --full
+  run benchdrv 300 python bench.py --full --steps 20 --warmup 5
+  run c4 300 python bench.py --full --workload c4
   # (the list launches with the parameter copy, switched on at 50 / 25 % live: PDENV_COMPACT_AT)
-  PDENV_COMPACT_AT=0.5 run c4_at50 300 python bench.py --workload c4 --cpu-baseline 0
-  PDENV_COMPACT_AT=0.25 run c4_at25 300 python bench.py --workload c4 --cpu-baseline 0
-  run c5 300 python bench.py --workload c5
-  run c2 300 python bench.py --workload c2 --cpu-baseline 0
+  PDENV_COMPACT_AT=0.5 run c4_at50 300 python bench.py --full --workload c4 --cpu-baseline 0
+  PDENV_COMPACT_AT=0.25 run c4_at25 300 python bench.py --full --workload c4 --cpu-baseline 0
+  run c5 300 python bench.py --full --workload c5
+  run c2 300 python bench.py --full --workload c2 --cpu-baseline 0
   STAGES="prof profdrv profc4 profc5" run profs 600 bash tools/gpu_session.sh
   run pmc 600 bash tools/pmc_r03b.sh ;;
 13)
@@ -153,10 +153,10 @@ case "${PART:-1}" in
   PDENV_LIB=$L run pwc_tests 300 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -q --timeout 200 --timeout-method thread \
       -k "compaction_invariant or policy_rollout or pso_driver"
   for r in 1 2; do
-    PDENV_LIB=$L run pwc_c4_off_r$r 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
-    PDENV_LIB=$L PDENV_COMPACT_AT=0.5 run pwc_c4_at50_r$r 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
-    PDENV_LIB=$L PDENV_COMPACT_AT=0.25 run pwc_c4_at25_r$r 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
-    PDENV_LIB=$L PDENV_COMPACT=1 run pwc_c4_list_r$r 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    PDENV_LIB=$L run pwc_c4_off_r$r 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    PDENV_LIB=$L PDENV_COMPACT_AT=0.5 run pwc_c4_at50_r$r 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    PDENV_LIB=$L PDENV_COMPACT_AT=0.25 run pwc_c4_at25_r$r 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    PDENV_LIB=$L PDENV_COMPACT=1 run pwc_c4_list_r$r 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
   done ;;
 14)
   # the actor split over the env's lane pair (PD_ACTOR_SPLIT; libpdenv_nosplit: build_variant(
@@ -167,8 +167,8 @@ case "${PART:-1}" in
   run split_tests 500 python -u -m pytest tests/ -m gpu -x -q --timeout 200 --timeout-method thread \
       -k "policy or pso or compaction or actor or drivers"
   for r in 1 2; do
-    run split_c4_r$r 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
-    PDENV_LIB=$L run nosplit_c4_r$r 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    run split_c4_r$r 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    PDENV_LIB=$L run nosplit_c4_r$r 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
   done
   run plpe 300 python tools/policy_lpe_sweep.py
   STAGES="profc4" run profs 300 bash tools/gpu_session.sh ;;
@@ -180,10 +180,10 @@ case "${PART:-1}" in
   run exit_tests 500 python -u -m pytest tests/ -m gpu -x -q --timeout 200 --timeout-method thread \
       -k "policy or pso or compaction or actor or drivers"
   for r in 1 2; do
-    run exit_c4_f8_r$r 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
-    PDENV_LIB=$L run noexit_c4_f8_r$r 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
-    PDENV_PFUSE=16 run exit_c4_f16_r$r 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
-    PDENV_PFUSE=16 PDENV_LIB=$L run noexit_c4_f16_r$r 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    run exit_c4_f8_r$r 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    PDENV_LIB=$L run noexit_c4_f8_r$r 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    PDENV_PFUSE=16 run exit_c4_f16_r$r 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    PDENV_PFUSE=16 PDENV_LIB=$L run noexit_c4_f16_r$r 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
   done ;;
 16)
   # part 15 and the final measurement (part 12) in one call: the suite and smoke; c4 with and
@@ -193,15 +193,15 @@ case "${PART:-1}" in
   run gpu_tests 600 python -u -m pytest tests/ -m gpu -x -q --timeout 200 --timeout-method thread
   run smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
   for r in 1 2; do
-    run exit_c4_f8_r$r 200 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
-    PDENV_LIB=$L run noexit_c4_f8_r$r 200 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
-    PDENV_PFUSE=16 run exit_c4_f16_r$r 200 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    run exit_c4_f8_r$r 200 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    PDENV_LIB=$L run noexit_c4_f8_r$r 200 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    PDENV_PFUSE=16 run exit_c4_f16_r$r 200 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
   done
-  run bench 300 python bench.py
-  run benchdrv 200 python bench.py --steps 20 --warmup 5
-  run c4 200 python bench.py --workload c4
-  run c5 200 python bench.py --workload c5
-  run c2 200 python bench.py --workload c2 --cpu-baseline 0
+  run bench 300 python bench.py --full
+  run benchdrv 200 python bench.py --full --steps 20 --warmup 5
+  run c4 200 python bench.py --full --workload c4
+  run c5 200 python bench.py --full --workload c5
+  run c2 200 python bench.py --full --workload c2 --cpu-baseline 0
   STAGES="prof profdrv profc4 profc5" run profs 500 bash tools/gpu_session.sh
   run pmc 500 bash tools/pmc_r03b.sh ;;
 17)
@@ -210,24 +210,24 @@ case "${PART:-1}" in
   run pf_tests 500 python -u -m pytest tests/ -m gpu -x -q --timeout 200 --timeout-method thread \
       -k "policy or pso or compaction or actor or drivers"
   for r in 1 2; do for f in 16 32 64; do
-    PDENV_PFUSE=$f run pf${f}_c4_r$r 200 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
+    PDENV_PFUSE=$f run pf${f}_c4_r$r 200 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0
   done; done
-  run c4 200 python bench.py --workload c4
+  run c4 200 python bench.py --full --workload c4
   STAGES="profc4" run profs 300 bash tools/gpu_session.sh ;;
 18)
   # the final build (64 policy steps per launch, part 17): the suite and smoke, c4 (two rounds and
   # the line), its trace, the bench lines
   run gpu_tests 600 python -u -m pytest tests/ -m gpu -x -q --timeout 200 --timeout-method thread
   run smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
-  for r in 1 2; do run pf64_c4_r$r 200 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0; done
-  run c4 200 python bench.py --workload c4
-  run bench 300 python bench.py
-  run benchdrv 200 python bench.py --steps 20 --warmup 5
+  for r in 1 2; do run pf64_c4_r$r 200 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0; done
+  run c4 200 python bench.py --full --workload c4
+  run bench 300 python bench.py --full
+  run benchdrv 200 python bench.py --full --steps 20 --warmup 5
   STAGES="profc4 prof profdrv" run profs 400 bash tools/gpu_session.sh ;;
 19)
   # the committed tree as the round-end driver runs it: the GPU suite, smoke, the default bench line
   run gpu_tests 600 python -u -m pytest tests/ -m gpu -x -q --timeout 200 --timeout-method thread
   run smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
-  run bench 300 python bench.py ;;
+  run bench 300 python bench.py --full ;;
 esac
 echo "=== done"

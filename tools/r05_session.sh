@@ -90,7 +90,7 @@ run() {  # name, seconds, command...
 }
 case "${PART:-1}" in
 1)
-  run benchdrv 300 python bench.py --steps 20 --warmup 5
+  run benchdrv 300 python bench.py --full --steps 20 --warmup 5
   for f in 20 128 4 1; do
     L=$(( f >= 20 ? 6 : 24 ))
     BURN=640 FUSE=$f LAUNCHES=$L run fix_f$f 200 python tools/time_fused.py
@@ -101,8 +101,8 @@ case "${PART:-1}" in
   # (the records of part 1 came from the pre-ABI-9 library, where the PDENV_COMPACT environment
   # switch chose the live list; ABI 9 removed every getenv switch, so the same comparison is now
   # made with the tuning flags below -- refill off, list on / off)
-  run c4_262k_list 300 python bench.py --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0 --policy-list 1 --policy-refill 0
-  run c4_262k_nolist 300 python bench.py --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0 --policy-list 0 --policy-refill 0
+  run c4_262k_list 300 python bench.py --full --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0 --policy-list 1 --policy-refill 0
+  run c4_262k_nolist 300 python bench.py --full --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0 --policy-list 0 --policy-refill 0
   ;;
 2)
   # the ABI-9 build (launcher checks, two-step divisions where the divisor needs them, tuning and
@@ -150,9 +150,9 @@ case "${PART:-1}" in
     BURN=640 FUSE=$f LAUNCHES=$L run fix5_f$f 200 python tools/time_fused.py
   done
   BURN=640 FUSE=128 LAUNCHES=6 PREC=f32 run t5_f32 200 python tools/time_fused.py
-  run benchdrv5 300 python bench.py --steps 20 --warmup 5
-  run c5_5 300 python bench.py --workload c5
-  run c4_262k_5 300 python bench.py --workload c4 --particles 262144 --steps 6 --warmup 2 --policy-list 0
+  run benchdrv5 300 python bench.py --full --steps 20 --warmup 5
+  run c5_5 300 python bench.py --full --workload c5
+  run c4_262k_5 300 python bench.py --full --workload c4 --particles 262144 --steps 6 --warmup 2 --policy-list 0
   ;;
 6)
   # the build with the env state requested ahead of the table staging (and of the SAC actor):
@@ -165,7 +165,7 @@ case "${PART:-1}" in
     L=$(( f >= 20 ? 6 : 24 ))
     BURN=640 FUSE=$f LAUNCHES=$L run fix6_f$f 200 python tools/time_fused.py
   done
-  run benchdrv6 300 python bench.py --steps 20 --warmup 5
+  run benchdrv6 300 python bench.py --full --steps 20 --warmup 5
   PART=4 bash tools/r05_session.sh
   ;;
 7)
@@ -175,8 +175,8 @@ case "${PART:-1}" in
   run gpu_t7 900 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -v --timeout 300 --timeout-method thread \
       -k "compaction or info_tap or launcher" -s
   run diag_lb 200 python tools/diag_f32_lb.py
-  run c4_262k_refill 300 python bench.py --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0
-  run c4_32k 300 python bench.py --workload c4 --steps 8 --warmup 2 --cpu-baseline 0
+  run c4_262k_refill 300 python bench.py --full --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0
+  run c4_32k 300 python bench.py --full --workload c4 --steps 8 --warmup 2 --cpu-baseline 0
   V=psso-sac-for-powered-descent_amd/pdenv/libpdenv_idx2.so
   CASES="d_idx2:1:0:$V c_idx2:0:0:$V c_fine:0:0" run pmc7 900 bash tools/pmc_r05.sh
   ;;
@@ -188,27 +188,27 @@ case "${PART:-1}" in
   run gpu_t8 900 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -v --timeout 300 --timeout-method thread \
       -k "compaction or info_tap or launcher or f32_teacher" -s
   for b in 0 1 4 8 16 32; do
-    run c4_262k_rf$b 300 python bench.py --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0 --policy-refill $b
+    run c4_262k_rf$b 300 python bench.py --full --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0 --policy-refill $b
   done
   for b in 0 8; do
-    run c4_32k_rf$b 300 python bench.py --workload c4 --steps 8 --warmup 2 --cpu-baseline 0 --policy-refill $b
+    run c4_32k_rf$b 300 python bench.py --full --workload c4 --steps 8 --warmup 2 --cpu-baseline 0 --policy-refill $b
   done
   ;;
 9)
   run gpu_t9 900 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -v --timeout 300 --timeout-method thread \
       -k "compaction or info_tap or launcher or f32_teacher" -s
-  run c4_262k_auto 300 python bench.py --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0
+  run c4_262k_auto 300 python bench.py --full --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0
   for b in 12 24; do
-    run c4_262k_rf$b 300 python bench.py --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0 --policy-refill $b
+    run c4_262k_rf$b 300 python bench.py --full --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0 --policy-refill $b
   done
   ;;
 10)
   run gpu_tests 1000 python -u -m pytest tests/ -m gpu -x -q --timeout 300 --timeout-method thread -s
   run smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
   run mlp_clocks 120 tools/bin/mlp_clocks
-  run c4_262k_b24 300 python bench.py --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0
-  run c4_262k_b0 300 python bench.py --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0 --policy-refill 0
-  run benchdrv10 300 python bench.py --steps 20 --warmup 5
+  run c4_262k_b24 300 python bench.py --full --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0
+  run c4_262k_b0 300 python bench.py --full --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0 --policy-refill 0
+  run benchdrv10 300 python bench.py --full --steps 20 --warmup 5
   ;;
 11)
   for b in mlp_clocks mlp_clocks_v2 mlp_clocks_v2_kd2 mlp_clocks_v2_kd8 mlp_clocks_v2_kd16 mlp_clocks_v2_nt2kd8 \
@@ -221,7 +221,7 @@ case "${PART:-1}" in
     run clk12_$b 60 tools/bin/$b
   done
   run gpu_sac 600 python -u -m pytest tests/ -m gpu -x -q --timeout 300 --timeout-method thread -k "sac or actor or c5" -s
-  run c5_12 300 python bench.py --workload c5
+  run c5_12 300 python bench.py --full --workload c5
   run c5_breakdown12 300 python tools/c5_breakdown.py
   ;;
 13)
@@ -260,12 +260,12 @@ case "${PART:-1}" in
 23)
   run gpu_sac23 600 python -u -m pytest tests/ -m gpu -x -q --timeout 300 --timeout-method thread -k "sac or actor or c5" -s
   run clk23_product 60 tools/bin/mlp_clocks
-  run c5_23 300 python bench.py --workload c5
+  run c5_23 300 python bench.py --full --workload c5
   run c5_breakdown23 300 python tools/c5_breakdown.py
   ;;
 24)
   run gpu_sac24 600 python -u -m pytest tests/ -m gpu -x -q --timeout 300 --timeout-method thread -k "sac or actor or c5 or fused" -s
-  run c5_24 300 python bench.py --workload c5
+  run c5_24 300 python bench.py --full --workload c5
   run c5_breakdown24 300 python tools/c5_breakdown.py
   BURN=640 FUSE=1 LAUNCHES=24 run fix24_f1 200 python tools/time_fused.py
   ;;
@@ -274,19 +274,19 @@ case "${PART:-1}" in
       -k "compaction or launcher" -s
   for c in "-1 -1" "0 24" "50 24" "90 24" "100 24" "75 8" "90 8" "90 16"; do
     set -- $c
-    run c4_262k_own$1_b$2 300 python bench.py --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0 \
+    run c4_262k_own$1_b$2 300 python bench.py --full --workload c4 --particles 262144 --steps 6 --warmup 2 --cpu-baseline 0 \
         --policy-refill-own $1 --policy-refill $2
   done
   ;;
 26)
   run gpu_tests 1000 python -u -m pytest tests/ -m gpu -x -q --timeout 300 --timeout-method thread
   run smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
-  run bench 300 python bench.py
-  run benchdrv 200 python bench.py --steps 20 --warmup 5
-  run c4 200 python bench.py --workload c4
-  run c4_262k 300 python bench.py --workload c4 --particles 262144 --steps 8 --warmup 2
-  run c5 200 python bench.py --workload c5
-  run c2 200 python bench.py --workload c2 --cpu-baseline 0
+  run bench 300 python bench.py --full
+  run benchdrv 200 python bench.py --full --steps 20 --warmup 5
+  run c4 200 python bench.py --full --workload c4
+  run c4_262k 300 python bench.py --full --workload c4 --particles 262144 --steps 8 --warmup 2
+  run c5 200 python bench.py --full --workload c5
+  run c2 200 python bench.py --full --workload c2 --cpu-baseline 0
   ;;
 27)
   STAGES="prof profdrv profc4 profc5" run profs 800 bash tools/gpu_session.sh
@@ -308,7 +308,7 @@ case "${PART:-1}" in
       -k "compaction or launcher" -s
   for r in 1 2; do
     for o in 1 0; do
-      run c4_262k_order${o}_r$r 300 python bench.py --workload c4 --particles 262144 --steps 8 --warmup 3 --cpu-baseline 0 --policy-order $o
+      run c4_262k_order${o}_r$r 300 python bench.py --full --workload c4 --particles 262144 --steps 8 --warmup 3 --cpu-baseline 0 --policy-order $o
     done
   done
   PART=28 bash tools/r05_session.sh
@@ -330,7 +330,7 @@ case "${PART:-1}" in
   for r in 1 2; do for d in 0 1; do
     DESCENT=$d BURN=640 FUSE=128 LAUNCHES=6 run t32_r${r}_d$d 200 python tools/time_fused.py
   done; done
-  run benchdrv32 200 python bench.py --steps 20 --warmup 5
+  run benchdrv32 200 python bench.py --full --steps 20 --warmup 5
   ;;
 33)
   PART=26 bash tools/r05_session.sh
@@ -352,21 +352,21 @@ case "${PART:-1}" in
 36)
   for r in 1 2; do
     for b in 0 24; do
-      run c4_32k_36_rf${b}_r$r 300 python bench.py --workload c4 --steps 32 --warmup 4 --cpu-baseline 0 --policy-refill $b
+      run c4_32k_36_rf${b}_r$r 300 python bench.py --full --workload c4 --steps 32 --warmup 4 --cpu-baseline 0 --policy-refill $b
     done
   done
   ;;
 37)
   run clk37_v10 60 tools/bin/mlp_clocks_v10
   run gpu_sac37 600 python -u -m pytest tests/ -m gpu -x -q --timeout 300 --timeout-method thread -k "sac or actor or c5 or fused" -s
-  run c5_37 300 python bench.py --workload c5
+  run c5_37 300 python bench.py --full --workload c5
   run c5_breakdown37 300 python tools/c5_breakdown.py
   ;;
 38)
   run gpu_pol38 900 python -u -m pytest tests/ -m gpu -x -q --timeout 300 --timeout-method thread \
       -k "policy or pso or compaction or c4 or drivers or swarm" -s
-  run c4_38 300 python bench.py --workload c4
-  run c4_262k_38 300 python bench.py --workload c4 --particles 262144 --steps 8 --warmup 2 --cpu-baseline 0
+  run c4_38 300 python bench.py --full --workload c4
+  run c4_262k_38 300 python bench.py --full --workload c4 --particles 262144 --steps 8 --warmup 2 --cpu-baseline 0
   ;;
 39)
   PART=26 bash tools/r05_session.sh
@@ -388,8 +388,8 @@ case "${PART:-1}" in
   ;;
 42)
   for r in 1 2 3; do
-    run c5g1_$r 200 python bench.py --workload c5 --cpu-baseline 0 --graph 1
-    run c5g0_$r 200 python bench.py --workload c5 --cpu-baseline 0 --graph 0
+    run c5g1_$r 200 python bench.py --full --workload c5 --cpu-baseline 0 --graph 1
+    run c5g0_$r 200 python bench.py --full --workload c5 --cpu-baseline 0 --graph 0
   done
   for g in 1 0; do
     run c5trace_g$g 300 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/c5trace_g$g -o run -- python3 bench.py --workload c5 --cpu-baseline 0 --steps 192 --warmup 32 --graph $g
@@ -397,20 +397,20 @@ case "${PART:-1}" in
   ;;
 43)
   run gpu_sac43 600 python -u -m pytest tests/ -m gpu -x -q --timeout 300 --timeout-method thread -k "sac or actor or c5 or collector" -s
-  run c5_43a 300 python bench.py --workload c5
-  run c5_43b 300 python bench.py --workload c5
-  run bench43 600 python bench.py
+  run c5_43a 300 python bench.py --full --workload c5
+  run c5_43b 300 python bench.py --full --workload c5
+  run bench43 600 python bench.py --full
   ;;
 44)
-  run c5_44a 300 python bench.py --workload c5
-  run c5_44b 300 python bench.py --workload c5
+  run c5_44a 300 python bench.py --full --workload c5
+  run c5_44b 300 python bench.py --full --workload c5
   run c5prof44 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/c5prof44 -o run -- python3 bench.py --workload c5
   ;;
 45)
   run gpu_pso45 900 python -u -m pytest tests/ -m gpu -x -q --timeout 300 --timeout-method thread \
       -k "policy or pso or compaction or c4 or drivers or swarm or migrat or share" -s
-  run c4_45a 300 python bench.py --workload c4
-  run c4_45b 300 python bench.py --workload c4
+  run c4_45a 300 python bench.py --full --workload c4
+  run c4_45b 300 python bench.py --full --workload c4
   STAGES="profc4" run profs45 800 bash tools/gpu_session.sh
   ;;
 46|47|48|49|51)

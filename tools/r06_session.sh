@@ -65,7 +65,7 @@ run() {  # name, seconds, command...
 rccl() {  # name, args...
   local name=$1; shift
   PD_BENCH_DIST=1 run rccl_$name 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-      --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 "$@"
+      --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 "$@"
 }
 case "${PART:-1}" in
 1)
@@ -75,7 +75,7 @@ case "${PART:-1}" in
   for r in 1 2; do
     for v in r06 r05; do
       lib=$PKG/libpdenv.so; [ $v = r05 ] && lib=$PKG/libpdenv_r05.so
-      PDENV_LIB=$lib run benchdrv_${v}_r$r 200 python bench.py --steps 20 --warmup 5 --secondary 0 --descent 0 --others 0 --cpu-baseline 0 --fresh 0
+      PDENV_LIB=$lib run benchdrv_${v}_r$r 200 python bench.py --full --steps 20 --warmup 5 --secondary 0 --descent 0 --others 0 --cpu-baseline 0 --fresh 0
       for f in 20 128; do
         PDENV_LIB=$lib BURN=640 FUSE=$f LAUNCHES=6 run fix_${v}_f${f}_r$r 200 python tools/time_fused.py
       done
@@ -95,8 +95,8 @@ case "${PART:-1}" in
   for r in 1 2; do
     for v in base pnt; do
       lib=$PKG/libpdenv.so; [ $v != base ] && lib=$PKG/libpdenv_$v.so
-      PDENV_LIB=$lib run c4_${v}_r$r 300 python bench.py --workload c4 --steps 8 --warmup 2 --cpu-baseline 0
-      PDENV_LIB=$lib run c4big_${v}_r$r 300 python bench.py --workload c4 --particles 262144 --steps 4 --warmup 1 --cpu-baseline 0
+      PDENV_LIB=$lib run c4_${v}_r$r 300 python bench.py --full --workload c4 --steps 8 --warmup 2 --cpu-baseline 0
+      PDENV_LIB=$lib run c4big_${v}_r$r 300 python bench.py --full --workload c4 --particles 262144 --steps 4 --warmup 1 --cpu-baseline 0
     done
     for v in base fnt; do
       lib=$PKG/libpdenv.so; [ $v != base ] && lib=$PKG/libpdenv_$v.so
@@ -105,9 +105,9 @@ case "${PART:-1}" in
       done
     done
   done
-  run c2 300 python bench.py --workload c2
-  run c2rk4 300 python bench.py --workload c2 --integrator rk4
-  run c5 300 python bench.py --workload c5
+  run c2 300 python bench.py --full --workload c2
+  run c2rk4 300 python bench.py --full --workload c2 --integrator rk4
+  run c5 300 python bench.py --full --workload c5
   ;;
 4)
   PA="SQ_INSTS_VALU SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32"
@@ -137,22 +137,22 @@ case "${PART:-1}" in
   done
   ;;
 6)
-  run benchdrv6a 400 python bench.py --steps 20 --warmup 5
-  run benchdrv6b 400 python bench.py --steps 20 --warmup 5
-  run bench6 400 python bench.py
+  run benchdrv6a 400 python bench.py --full --steps 20 --warmup 5
+  run benchdrv6b 400 python bench.py --full --steps 20 --warmup 5
+  run bench6 400 python bench.py --full
   ;;
 7)
   run gpu_tests 1200 python -u -m pytest tests/ -m gpu -x -q --timeout 600 --timeout-method thread
   run smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
-  run bench 400 python bench.py
-  run benchdrv 400 python bench.py --steps 20 --warmup 5
-  run c4 300 python bench.py --workload c4
-  run c4_262k 300 python bench.py --workload c4 --particles 262144 --steps 8 --warmup 2
-  run c5 300 python bench.py --workload c5
-  run c2 300 python bench.py --workload c2
-  run c2rk4 300 python bench.py --workload c2 --integrator rk4
+  run bench 400 python bench.py --full
+  run benchdrv 400 python bench.py --full --steps 20 --warmup 5
+  run c4 300 python bench.py --full --workload c4
+  run c4_262k 300 python bench.py --full --workload c4 --particles 262144 --steps 8 --warmup 2
+  run c5 300 python bench.py --full --workload c5
+  run c2 300 python bench.py --full --workload c2
+  run c2rk4 300 python bench.py --full --workload c2 --integrator rk4
   PD_BENCH_BACKEND=gloo run gloo2 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-      --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 2 --steps 32 --warmup 8 --descent 0 --fresh 0 --staggered 0
+      --master-addr 127.0.0.1 --master-port 29519 bench.py --full --gpus 2 --steps 32 --warmup 8 --descent 0 --fresh 0 --staggered 0
   ;;
 8)
   run gpu_ins 300 python -u -m pytest tests/test_gpu_parity.py -x -v --timeout 200 --timeout-method thread -k "inserts_its_misses or device_solve"
@@ -181,8 +181,8 @@ case "${PART:-1}" in
   for r in 1 2; do
     for v in new base; do
       lib=$PKG/libpdenv.so; [ $v = base ] && lib=$PKG/libpdenv_base.so
-      PDENV_LIB=$lib run c4_${v}_r$r 300 python bench.py --workload c4 --steps 8 --warmup 2 --cpu-baseline 0
-      PDENV_LIB=$lib run c4big_${v}_r$r 300 python bench.py --workload c4 --particles 262144 --steps 4 --warmup 1 --cpu-baseline 0
+      PDENV_LIB=$lib run c4_${v}_r$r 300 python bench.py --full --workload c4 --steps 8 --warmup 2 --cpu-baseline 0
+      PDENV_LIB=$lib run c4big_${v}_r$r 300 python bench.py --full --workload c4 --particles 262144 --steps 4 --warmup 1 --cpu-baseline 0
     done
   done
   ;;

@@ -13,6 +13,6 @@ run() {  # name, args...
   echo "== $name rc=$rc"; tail -n 2 gpurun_out/rccl_$name.log
   [ $rc -eq 0 ] || exit $rc
 }
-run c3 --steps 32 --warmup 16 --cpu-baseline 0 --secondary 0
-run c5 --workload c5 --steps 32 --warmup 8
-run c4 --workload c4 --steps 2 --warmup 1 --cpu-baseline 0
+run c3 --full --steps 32 --warmup 16 --cpu-baseline 0 --secondary 0
+run c5 --full --workload c5 --steps 32 --warmup 8
+run c4 --full --workload c4 --steps 2 --warmup 1 --cpu-baseline 0
