@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PD_ABI_VERSION 11  /* 4: pd_config.integrator (was padding); 5: pd_count_work, pd_step_sac; 6: cell pieces (pd_cell_piece_info, stats word 44); 7: pd_step_sac_ring, pd_sac_actor, stats word 45; 8: pd_step_sac_fused, pd_atm_table; 9: pd_config.table_flags, pd_tuning, caller scratch for pd_pso_swarm_minima, state/action dims of pd_step_sac_fused; 10: step launches insert their own solved misses (pd_flush_misses optional), explicit list settings turn the auto refill off; 11: pd_pso_step_chunked, pd_rollout_policy_chunked */
+#define PD_ABI_VERSION 11  /* 4: pd_config.integrator (was padding); 5: pd_count_work, pd_step_sac; 6: cell pieces (pd_cell_piece_info, stats word 44); 7: pd_step_sac_ring, pd_sac_actor, stats word 45; 8: pd_step_sac_fused, pd_atm_table; 9: pd_config.table_flags, pd_tuning, caller scratch for pd_pso_swarm_minima, state/action dims of pd_step_sac_fused; 10: step launches insert their own solved misses (pd_flush_misses optional), explicit list settings turn the auto refill off; 11: pd_pso_step_chunked, pd_rollout_policy_chunked; pd_rollout_sac added later as an additive export (the version stays 11: no layout or existing call changes) */
 #define PD_MAX_PTS 256      /* aero scatter points per table */
 #define PD_MAX_COLS 5       /* AoA columns per aero table */
 #define PD_MAX_TAB 64       /* grid-fin table length */
@@ -317,6 +317,41 @@ pd_status pd_step_sac_fused(pd_env* env, int32_t state_dim, int32_t action_dim, 
                             float max_action, float* eps_out, float* action, float* ring, int64_t capacity,
                             long long* ring_state, float* priorities, const float* max_priority, float* obs32,
                             void* stream);
+/* Evaluation rollouts of a SAC actor, whole episodes on the device: the driver's evaluate_agent
+ * (sac_pytorch_powered_descent.py:234-251: reset, select_action(state, deterministic=True) until
+ * done or truncated, total_reward += reward, done counted as a landing) and the loop of
+ * visualize_trajectory (:354-376, which keeps the traces), one env per episode.  The actor's
+ * forward pass (pd_sac_actor's, the same bits) runs INSIDE the fused-step loop of the step kernel,
+ * once per step, on the float32 observation of the env's register state; sampling and the step
+ * are pd_step_sac_fused's: the results equal a loop of pd_step_sac_fused calls bit for bit.
+ *  state_dim .. params: as pd_step_sac_fused (same checks); hidden 128 or 256
+ *  deterministic: != 0: action = tanh(mean) max_action; 0: eps drawn in the kernel as
+ *            pd_step_sac_ring draws it (Philox keyed by env, episode, step)
+ *  reset_first: != 0: every env is reset first, as by pd_reset; 0: the episodes start from the
+ *            handle's current state (pd_set_state, a checkpoint, a previous capped call)
+ *  max_steps: the cap on every episode's length in this call
+ *  ret     : [N] handle precision, the rewards added in step order; steps: [N] int32 episode
+ *            lengths; done: [N] uint8, the terminal step's done; trunc_id: [N] int8, the terminal
+ *            step's truncation id.  ret and steps are zeroed at the call's start.
+ *  actions_out: [max_steps][N][A] float32; rewards_out: [max_steps][N] handle precision; row t
+ *            of env i is written only for t < steps[i]
+ *  Each of the six outputs may be NULL.
+ * An env whose step returns done or truncated is stored once with its terminal (pre-reset) state
+ * and freezes: it is never auto-reset, whatever pd_config.auto_reset says.  An env that reaches
+ * max_steps without ending has steps = max_steps, done = 0, trunc_id as its last step left it and
+ * the state after max_steps steps; a following call with reset_first = 0 continues it
+ * bit-identically.  The rollout is a chain of launches of at most pd_tuning.step_fuse steps (each
+ * inserting the neighbourhoods it solved); a workgroup leaves a launch's step loop once none of
+ * its 16 envs is live.  Results do not depend on step_fuse.  No host synchronisation.
+ * Handle requirements: those of pd_step_sac_fused (RL landing burns, reference integrator,
+ * float32 actions).  PD_ERR_UNSUPPORTED, with nothing launched and the cause in pd_last_error, for
+ * a handle that does not step 16 lanes per env and for hidden 512 (callers take the per-step
+ * path: pd_step_sac_fused / pd_step_sac_ring).  (additive export, ABI 11) */
+pd_status pd_rollout_sac(pd_env* env, int32_t state_dim, int32_t action_dim, int32_t hidden,
+                         int32_t n_hidden_layers, const float* const* params, int32_t deterministic,
+                         float log_std_min, float log_std_max, float max_action, int32_t reset_first,
+                         int32_t max_steps, void* ret, int32_t* steps, uint8_t* done, int8_t* trunc_id,
+                         float* actions_out, void* rewards_out, void* stream);
 /* Multi-step rollout with device-resident actions [T][N][A]: the fused launches of pd_step_n
  * (per-step launches for the other phases), rewards accumulated into reward_sum [N] (may be
  * NULL), no per-step outputs.  No host synchronisation. */

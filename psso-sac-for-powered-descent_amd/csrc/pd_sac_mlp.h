@@ -68,11 +68,14 @@ template <int H> constexpr int sac_mlp_lds_floats() {
 // array: the LDS DMA of the hidden layers addresses it as LDS).  MA: SacMlp
 // in any address space (the step kernel reads it from its kernarg segment).  mark(k): called by
 // every thread at the end of phase k (0 layer 1, l hidden layer l, L the heads) -- the section
-// clocks of tools/mlp_clocks.hip; the product passes none.
+// clocks of tools/mlp_clocks.hip; the product passes none.  obs_lds: the tile's observations
+// [16][S] in LDS instead of a.obs (the SAC rollout kernel, whose envs' states live in registers
+// between its steps; written before a workgroup barrier by the caller): the same floats take
+// the same path from there on, so the heads are the same bits.
 struct NoMark { __device__ void operator()(int) const {} };
 template <int H, typename MA, typename Put, typename Mark = NoMark>
 __device__ __forceinline__ void sac_mlp_tile(const MA& a, int64_t n, int64_t e0, float* hb, Put&& put,
-                                             Mark&& mark = Mark{}) {
+                                             Mark&& mark = Mark{}, const float* obs_lds = nullptr) {
     constexpr int P = H + 4;
     float* h0 = hb;
     float* h1 = hb + kSacTile * P;
@@ -116,7 +119,8 @@ __device__ __forceinline__ void sac_mlp_tile(const MA& a, int64_t n, int64_t e0,
         }
         if (tid < kSacTile * s1) {
             const int te = tid / s1;
-            h1[tid] = e0 + te < n ? a.obs[(e0 + te) * s1 + (tid - te * s1)] : 0.f;
+            if (obs_lds) h1[tid] = obs_lds[tid];
+            else h1[tid] = e0 + te < n ? a.obs[(e0 + te) * s1 + (tid - te * s1)] : 0.f;
         }
         __syncthreads();
 #pragma unroll

@@ -290,11 +290,22 @@ template <typename R> struct StepArgs {
     uint32_t* refill_next;
     int refill, refill_base, refill_max;
     int refill_slots, refill_q;   // (the slots; particles of a wave's own range, [w Q, (w + 1) Q))
+    // pd_rollout_sac (k_step<..., SAC, ROLL>, 16 lanes per env): whole actor-driven episodes, the
+    // actor (sac_mlp) inside the fused-step loop.  An env whose step ends its episode is stored,
+    // flagged in b.fin and frozen; roll_t0: the steps of this call before this launch (row
+    // roll_t0 + f of the traces belongs to the launch's step f).  roll_ret [N] is read at the
+    // launch's start and written with steps / done / tid (each may be NULL) when the env freezes
+    // or the launch ends; roll_act [T][N][A], roll_rew [T][N]: the traces (NULL: none)
+    int roll_t0;
+    R* roll_ret; int32_t* roll_steps; uint8_t* roll_done; int8_t* roll_tid;
+    float* roll_act; R* roll_rew;
 };
 
 // Kernel launchers, explicitly instantiated in the kstep_*.hip translation units.
 template <typename R, int PH, int RT, bool W, int LPE, bool RK = false> void launch_step(const StepArgs<R>& a, hipStream_t s);
 template <typename R, int PH, bool W, int LPE> void launch_policy_lpe(const StepArgs<R>& a, int64_t n_launch,
                                                                       hipStream_t s);
+// the SAC rollout kernel (RL landing burns, 16 lanes per env), in translation units of its own
+template <typename R, int PH, bool W> void launch_sac_roll(const StepArgs<R>& a, hipStream_t s);
 
 }  // namespace pd

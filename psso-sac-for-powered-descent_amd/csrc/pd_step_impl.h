@@ -1077,12 +1077,22 @@ __device__ __forceinline__ TabView<R> tab_view(DP<R>& P, const R* tab, int table
 // CNT: the counting instantiation (pd_count_work; LPE 2 step kernels): without it every counting
 // site folds away.  SAC: the pd_step_sac instantiation (RL landing burns): action sampling from
 // the actor heads and the float32 transition-slab / next-observation epilogue
+// ROLL: the pd_rollout_sac instantiation (SAC, 16 lanes per env): whole actor-driven episodes.
+// The actor's forward pass runs inside the fused-step loop, once per step, on the float32
+// observation of the register state (what obs32 would hold on the per-step path: the same
+// bits as a loop of pd_step_sac_fused launches); an env whose step ends its episode is stored
+// with its terminal state, flagged in b.fin and frozen (never auto-reset), its lanes convergent
+// as frozen policy-rollout lanes are; the loop ends, workgroup-uniform, when the workgroup has
+// no live env left.  Per env: the return (rewards added in step order, a register), the episode
+// length, the terminal done and trunc_id, and optional action / reward traces.
 template <typename R, int PHASE, int RTD, bool WIND, int LPE, int POL = 0, bool RK4 = false, bool CNT = false,
-          bool SAC = false>
+          bool SAC = false, bool ROLL = false>
 // waves_per_eu(2): caps VGPR+AGPR at 256 so the f64 kernel keeps two waves per SIMD
 __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
     SA<R>& a = kargs<R>();
     static_assert(sizeof(a_) > 0);
+    static_assert(!ROLL || (SAC && LPE == 16 && !POL && !RK4 && !CNT && RTD == 0 && PHASE <= 1),
+                  "ROLL: the SAC kernel of the RL landing burns at 16 lanes per env");
     constexpr int EPB = kStepBlock / LPE;   // envs per workgroup
     __shared__ StepLds<R, WIND, EPB, LPE == 2> L;
 #ifdef PD_STAMP
@@ -1140,6 +1150,8 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
     if constexpr (POL) {
         if (!a.use_list) live = live && ev(a.b.fin, ui) == 0;
     }
+    // ROLL: an env that ended in an earlier launch of the rollout stays frozen
+    if constexpr (ROLL) live = live && ev(a.b.fin, ui) == 0;
     // role -> (table, part): LPE 1: both tables on one lane; else table = role / (LPE/2)
     constexpr int nparts = LPE >= 2 ? LPE / 2 : 1;
     const int my_table = LPE >= 2 ? role / nparts : 0;   // 0 = C_D, 1 = C_L
@@ -1211,7 +1223,10 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
     constexpr bool kSacMlp = SAC && LPE == 16;
     __shared__ __attribute__((aligned(16))) float s_mlp[kSacMlp ? sac_mlp_lds_floats<256>() : 1];
     __shared__ float s_sach[kSacMlp ? kSacTile * 16 : 1];
-    if constexpr (kSacMlp) {
+    // ROLL: the tile's float32 observations [16][S] (S <= 16), written by the envs' role-0 lanes
+    // at the top of every step; the actor runs there, not in the prologue
+    __shared__ float s_obs[ROLL ? kSacTile * 16 : 1];
+    if constexpr (kSacMlp && !ROLL) {
         const int H = a.sac_mlp.H;   // (grid-uniform: the barriers inside are reached by every thread)
         if (H) {
             const int64_t e0 = (int64_t)blockIdx.x * kSacTile;
@@ -1316,6 +1331,20 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
         }
     }
     const int nf = a.n_fused;   // policy rollouts: finished envs freeze, stored at their last step
+    // ROLL: the env's return so far (zeroed at the call's start, carried between the launches of
+    // the chain in roll_ret) and the store of its results (role-0 lane of a live env)
+    R racc = R(0);
+    if constexpr (ROLL) { if (live) racc = ldv(a.roll_ret, ui); }
+    auto roll_store = [&](int steps, int dn_, int id_, bool fin_) {
+        if (role != 0) return;
+        uint32_t uo = ui;
+        asm volatile("" : "+v"(uo));
+        ev(a.roll_ret, uo) = racc;
+        if (a.roll_steps) ev(a.roll_steps, uo) = (int32_t)steps;
+        if (a.roll_done) ev(a.roll_done, uo) = (uint8_t)dn_;
+        if (a.roll_tid) ev(a.roll_tid, uo) = (int8_t)id_;
+        if (fin_) ev(a.b.fin, uo) = 1;
+    };
     WaveCount wc{CNT ? L.work[threadIdx.x >> 6] : nullptr};   // this wave's workload counts (CNT)
     // the atmosphere and speed of the state a sub-step ends in are computed right after its
     // integration (their work -- the table loads -- overlapping atan2's) and carried: to the next
@@ -1346,6 +1375,33 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
     double ud[A];
 #pragma unroll
     for (int k = 0; k < A; ++k) { uf[k] = 0.f; ud[k] = 0.0; }
+    if constexpr (ROLL) {
+        // the actor of this step: every env's role-0 lane writes the float32 observation of its
+        // register state (obs_eval in the handle's precision, cast: the value the per-step path
+        // leaves in obs32; frozen and past-the-end envs too, their heads are never used), then the
+        // workgroup's 16 rows are one MLP tile and the heads land in s_sach as in the prologue of
+        // pd_step_sac_fused
+        if (role == 0) {
+            DP<R>& Q = *params<R>(a.P);
+            constexpr int ok = PHASE == 0 ? 0 : 3;
+            obs_eval<R>(Q, ok, e.s, [&](int k, R v) { s_obs[le * obs_dim(ok) + k] = (float)v; });
+        }
+        // Workgroup-uniform exit (the barrier also orders the observation rows before the tile's
+        // reads): no env of the workgroup is live -> leave the loop and FALL THROUGH to the
+        // kernel's end.  No early return here or anywhere in this kernel: it is a non-POL kernel,
+        // whose last workgroup (by ticket, below) inserts the launch's solved neighbourhoods after
+        // a workgroup barrier every thread must reach -- a workgroup that returned would leave the
+        // ticket short and the miss queue unflushed, or hang the barrier
+        if (!__syncthreads_or(live ? 1 : 0)) break;
+        const int A2 = a.sac_mlp.A;
+        auto put = [&](int en, int o, float v) { s_sach[en * 16 + (o < A2 ? o : 8 + o - A2)] = v; };
+        // (every wave, also one with no live env, runs the tile: it synchronises the workgroup)
+        if (a.sac_mlp.H == 128) sac_mlp_tile<128>(a.sac_mlp, a.n, (int64_t)blockIdx.x * kSacTile, s_mlp, put, NoMark{}, s_obs);
+        else sac_mlp_tile<256>(a.sac_mlp, a.n, (int64_t)blockIdx.x * kSacTile, s_mlp, put, NoMark{}, s_obs);
+        __syncthreads();   // (the heads are in s_sach; s_mlp and s_obs are free again)
+    }
+    // ROLL: a wave with no live env skips the step (wave-uniform; no barrier inside)
+    if (!ROLL || __ballot(live) != 0ull) {
     if constexpr (POL) {
         // pso_wrapper.augment_state (env_wrapped_ea.py:97-123) of the current state in the
         // handle's precision, cast to float32 (simple_actor.forward), then the actor
@@ -1402,6 +1458,10 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
             }
             uf[k] = tanhf(xk) * a.sac_max;
             if (a.sac_act && role == 0 && live) ev(a.sac_act + k, ui * AD) = uf[k];
+            if constexpr (ROLL) {   // the action trace: row roll_t0 + f of [T][N][A]
+                if (a.roll_act && role == 0 && live)
+                    ev(a.roll_act + (size_t)(a.roll_t0 + f) * (size_t)N * (size_t)AD + k, ui * AD) = uf[k];
+            }
         }
     } else if (a.act_f64) {
 #pragma unroll
@@ -2060,7 +2120,8 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
     PD_T(t_rtd);
     PD_ACC(5, t_rtd - t_loop);
     // ---- outputs of step f (role 0 of the env's lane group)
-    const bool ended = !POL && a.auto_reset && (dn || tr);
+    // (ROLL: an episode's end freezes the env below, whatever cfg.auto_reset says)
+    const bool ended = !POL && !ROLL && a.auto_reset && (dn || tr);
     wc.add(kStResets - kStWork, ended && role == 0 && live);
     k_have = !ended;
     // (binary32: the next step starts from the rounded state; its speed from the rounded velocity,
@@ -2076,6 +2137,12 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
             obs_write<R>(P2, ok, s, a.obs + fo * obs_dim(ok), uo);
         }
         if (a.reward) ev(a.reward + fo, ui) = rew;
+        if constexpr (ROLL) {
+            // evaluate_agent's total_reward += reward (sac_pytorch_powered_descent.py:234-251),
+            // in step order in the handle's precision; the reward trace's row roll_t0 + f
+            racc += rew;
+            if (a.roll_rew) ev(a.roll_rew + (size_t)(a.roll_t0 + f) * (size_t)N, ui) = rew;
+        }
         if constexpr (POL) {
             // objective_function: episode_reward -= reward until done or truncated (env_wrapped_ea.py:200-222)
             ev(a.reward_sum, uo) -= rew;
@@ -2115,6 +2182,17 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
         const int ok = kObsKind >= 0 ? kObsKind : P2.obs_kind;
         const uint32_t S = (uint32_t)obs_dim(ok);
         obs_eval<R>(P2, ok, e.s, [&](int k, R v) { ev(a.obs32, ui * S + (uint32_t)k) = (float)v; });
+    }
+    if constexpr (ROLL) {
+        // `done or truncated` ends the episode: the env is stored once, with its terminal
+        // (pre-reset) state, its results written and b.fin set for the rollout's later launches;
+        // its lanes freeze -- convergent with the wave for the cooperative miss solve, writing
+        // nothing more
+        if (live && (dn || tr)) {
+            store_all();
+            roll_store(a.roll_t0 + f + 1, dn, id, true);
+            live = false;
+        }
     }
     if constexpr (POL) {
         // an episode that ended is stored now and its lanes freeze (they go on computing in step
@@ -2170,6 +2248,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
         // not F steps after the swarm's last episode
         if (__ballot(live) == 0ull) break;
     }
+    }   // (ROLL: the wave's step)
     }   // fused steps
     if constexpr (POL) {
         // done-mask compaction: the envs whose episode goes on, in lane order, appended to the
@@ -2189,6 +2268,9 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
 
     // ---- the env's state back to HBM, once (policy rollouts: also when its episode ends)
     PD_T(t_store);
+    // (ROLL: an env still live has run all nf steps of the launch -- the loop leaves early only
+    // with no live env -- and goes on in the rollout's next launch, or the caller's next call)
+    if constexpr (ROLL) { if (live) roll_store(a.roll_t0 + nf, 0, e.tid, false); }
     store_all();
     if constexpr (SAC) {
         // ring mode: the launch's last workgroup (a ticket per workgroup, taken after all of its
@@ -2270,6 +2352,12 @@ template <typename R, int PH, bool W, int LPE> void launch_policy_lpe(const Step
                                                                       hipStream_t s) {
     unsigned grid = (unsigned)((n_launch * LPE + kStepBlock - 1) / kStepBlock);
     hipLaunchKernelGGL((k_step<R, PH, 1, W, LPE, 1>), dim3(grid), dim3(kStepBlock), 0, s, a);
+}
+
+// pd_rollout_sac: one launch of the chain (a.n_fused steps at most), a workgroup per 16 envs
+template <typename R, int PH, bool W> void launch_sac_roll(const StepArgs<R>& a, hipStream_t s) {
+    unsigned grid = (unsigned)((a.n * 16 + kStepBlock - 1) / kStepBlock);
+    hipLaunchKernelGGL((k_step<R, PH, 0, W, 16, 0, false, false, true, true>), dim3(grid), dim3(kStepBlock), 0, s, a);
 }
 
 }  // namespace pd

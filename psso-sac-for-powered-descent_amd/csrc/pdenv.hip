@@ -1279,6 +1279,7 @@ struct pd_env {
     int obs_kind = 0;   // obs_write layout of the handle's observation
     int count_work = 0; // workload counters on (pd_count_work)
     float* sac_heads = nullptr;   // pd_step_sac_fused's two-launch path: the actor heads [N][2A]
+    void* roll_ret = nullptr;     // pd_rollout_sac without `ret`: the returns carried between its launches [N]
     float* pol_w4 = nullptr;      // policy rollouts: the actor parameters in chunks of four ([P/4][N][4])
     float* pol_wc = nullptr;      // policy rollouts' list launches: the live envs' actor parameters
     pd_tuning tune{128, 64, 2, -1, 0.0, -1, 0, -1, 0};   // launch tuning (pd_set_tuning)
@@ -1774,6 +1775,52 @@ pd_status step_impl(pd_env* e, const void* actions, void* obs, void* reward, uin
     }
     dispatch_step<R>(e, a, s);
     PD_HIP(hipGetLastError());
+    return PD_OK;
+}
+
+// pd_rollout_sac: whole episodes driven by the actor inside the step loop (k_step<..., SAC, ROLL>),
+// a chain of launches of at most pd_tuning.step_fuse steps -- each launch's last workgroup
+// inserts the neighbourhoods it solved, as in pd_step_n -- with no host synchronisation: a later
+// launch reads the b.fin flags, and a workgroup with no live env only falls through to the ticket
+template <typename R>
+pd_status rollout_sac_impl(pd_env* e, const SacIO& io, int reset_first, int32_t max_steps, void* ret, int32_t* steps,
+                           uint8_t* done, int8_t* tid, float* actions_out, void* rewards_out, hipStream_t s) {
+    const size_t N = (size_t)e->cfg.n_envs;
+    if (!ret) {
+        if (!e->roll_ret) {
+            PD_HIP(hipMalloc(&e->roll_ret, N * 8));
+            e->allocs.push_back(e->roll_ret);
+        }
+        ret = e->roll_ret;
+    }
+    if (reset_first) {   // pd_reset of every env (clears b.fin)
+        hipLaunchKernelGGL(k_reset<R>, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, make_args<R>(e),
+                           (const uint8_t*)nullptr);
+        PD_HIP(hipGetLastError());
+    } else {
+        PD_HIP(hipMemsetAsync(e->fin, 0, N, s));
+    }
+    PD_HIP(hipMemsetAsync(ret, 0, N * sizeof(R), s));
+    if (steps) PD_HIP(hipMemsetAsync(steps, 0, N * 4, s));
+    if (done) PD_HIP(hipMemsetAsync(done, 0, N, s));
+    // (an env that takes no step keeps the trunc_id its last step left)
+    if (tid) PD_HIP(hipMemcpyAsync(tid, e->tid, N, hipMemcpyDeviceToDevice, s));
+    const bool wind = e->cfg.enable_wind != 0;
+    const int K = e->tune.step_fuse;
+    for (int32_t t = 0; t < max_steps; t += K) {
+        StepArgs<R> a = make_args<R>(e);
+        a.n_fused = max_steps - t < K ? max_steps - t : K;
+        a.sac_lo = io.lo; a.sac_hi = io.hi; a.sac_max = io.max_action;
+        a.sac_hs = io.head_stride; a.sac_draw = io.draw; a.sac_mlp = io.mlp;
+        a.roll_t0 = t;
+        a.roll_ret = (R*)ret; a.roll_steps = steps; a.roll_done = done; a.roll_tid = tid;
+        a.roll_act = actions_out; a.roll_rew = (R*)rewards_out;
+        if (e->cfg.phase == PD_PHASE_PURE_THROTTLE) { if (wind) launch_sac_roll<R, 0, true>(a, s); else launch_sac_roll<R, 0, false>(a, s); }
+        else { if (wind) launch_sac_roll<R, 1, true>(a, s); else launch_sac_roll<R, 1, false>(a, s); }
+        PD_HIP(hipGetLastError());
+    }
+    // (b.fin means "frozen until reset" to the policy rollouts: left clear for whatever follows)
+    PD_HIP(hipMemsetAsync(e->fin, 0, N, s));
     return PD_OK;
 }
 
@@ -2285,6 +2332,49 @@ pd_status pd_step_sac_fused(pd_env* e, int32_t state_dim, int32_t action_dim, in
                                  (hipStream_t)stream, 1, &io);
     return step_impl<float>(e, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                             (hipStream_t)stream, 1, &io);
+}
+
+pd_status pd_rollout_sac(pd_env* e, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t n_hidden_layers,
+                         const float* const* params, int32_t deterministic, float log_std_min, float log_std_max,
+                         float max_action, int32_t reset_first, int32_t max_steps, void* ret, int32_t* steps,
+                         uint8_t* done, int8_t* trunc_id, float* actions_out, void* rewards_out, void* stream) {
+    if (!e || !params) return fail(PD_ERR_INVALID, "pd_rollout_sac: null env/params");
+    if (max_steps < 0) return fail(PD_ERR_INVALID, "pd_rollout_sac: max_steps < 0");
+    const int S = e->obs_dim, A = e->act_dim;
+    if (state_dim != S || action_dim != A)
+        return fail(PD_ERR_INVALID, "pd_rollout_sac: the actor's state_dim / action_dim differ from the handle's");
+    if (n_hidden_layers < 1 || n_hidden_layers > kSacMaxLayers || A > 8 || S > 16)
+        return fail(PD_ERR_INVALID, "pd_rollout_sac: 1..8 hidden layers, state_dim <= 16, action_dim <= 8");
+    if (hidden == 512)
+        return fail(PD_ERR_UNSUPPORTED, "pd_rollout_sac: hidden width 512 does not fit the rollout kernel's LDS tile "
+                                        "(128 or 256; use the per-step path, pd_step_sac_fused)");
+    if (hidden != 128 && hidden != 256) return fail(PD_ERR_UNSUPPORTED, "pd_rollout_sac: hidden width 128 or 256 only");
+    for (int k = 0; k < 2 * (n_hidden_layers + 2); ++k) {
+        if (!params[k]) return fail(PD_ERR_INVALID, "pd_rollout_sac: null parameter");
+        if ((uintptr_t)params[k] % 16 != 0) return fail(PD_ERR_UNSUPPORTED, "pd_rollout_sac: parameter not 16-byte aligned");
+    }
+    if (e->cfg.action_f64) return fail(PD_ERR_UNSUPPORTED, "pd_rollout_sac: float32 actions only (action_f64 = 0)");
+    if (e->cfg.rtd == PD_RTD_PSO || e->cfg.integrator != PD_INTEG_REFERENCE ||
+        (e->cfg.phase != PD_PHASE_PURE_THROTTLE && e->cfg.phase != PD_PHASE_LANDING_BURN))
+        return fail(PD_ERR_UNSUPPORTED, "pd_rollout_sac: the RL landing burns (reference integrator) only");
+    if (e->lpe != 16)
+        return fail(PD_ERR_UNSUPPORTED, "pd_rollout_sac: the handle does not step 16 lanes per env (the workgroup's 16 "
+                                        "envs are the actor's MLP tile; use the per-step path, pd_step_sac_fused)");
+    // the traces are addressed as row base + a 32-bit per-lane byte offset within the row
+    if ((uint64_t)e->cfg.n_envs * (uint64_t)A * 4ull >= (1ull << 32))
+        return fail(PD_ERR_INVALID, "pd_rollout_sac: n_envs x action_dim x 4 must be below 2^32 bytes");
+    PD_HIP(hipSetDevice(e->device));
+    SacIO io{nullptr, nullptr, nullptr, log_std_min, log_std_max, max_action, nullptr, nullptr, nullptr, (uint32_t)(2 * A)};
+    io.draw = deterministic ? 0 : 1;
+    io.mlp.S = S; io.mlp.L = n_hidden_layers; io.mlp.A = A; io.mlp.H = hidden; io.mlp.obs = nullptr;
+    for (int l = 0; l < n_hidden_layers; ++l) { io.mlp.w[l] = params[2 * l]; io.mlp.b[l] = params[2 * l + 1]; }
+    io.mlp.wm = params[2 * n_hidden_layers]; io.mlp.bm = params[2 * n_hidden_layers + 1];
+    io.mlp.ws = params[2 * n_hidden_layers + 2]; io.mlp.bs = params[2 * n_hidden_layers + 3];
+    if (e->rsize == 8)
+        return rollout_sac_impl<double>(e, io, reset_first, max_steps, ret, steps, done, trunc_id, actions_out,
+                                        rewards_out, (hipStream_t)stream);
+    return rollout_sac_impl<float>(e, io, reset_first, max_steps, ret, steps, done, trunc_id, actions_out, rewards_out,
+                                   (hipStream_t)stream);
 }
 
 pd_status pd_step_n(pd_env* e, const void* actions, int32_t n_steps, void* obs, void* reward, uint8_t* done,

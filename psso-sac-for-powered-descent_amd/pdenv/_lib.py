@@ -99,7 +99,8 @@ EXPORTS = ["pd_abi_version", "pd_sizeof_params", "pd_sizeof_config", "pd_last_er
            "pd_checkpoint_load", "pd_counters", "pd_stats", "pd_count_work", "pd_atmosphere", "pd_obs_dim",
            "pd_action_dim", "pd_step_sac", "pd_pso_swarm_minima", "pd_pso_update_bests", "pd_cell_piece_info",
            "pd_step_sac_ring", "pd_sac_actor", "pd_step_sac_fused", "pd_atm_table", "pd_set_tuning", "pd_get_tuning",
-           "pd_pso_swarm_minima_scratch_bytes", "pd_step_n_info", "pd_pso_step_chunked", "pd_rollout_policy_chunked"]
+           "pd_pso_swarm_minima_scratch_bytes", "pd_step_n_info", "pd_pso_step_chunked", "pd_rollout_policy_chunked",
+           "pd_rollout_sac"]
 ABI_VERSION = 11
 
 _lib = None
@@ -136,6 +137,8 @@ def load(path=None):
     L.pd_sac_actor.argtypes = [I64, I32, I32, I32, I32, vp, vp, vp, vp]
     L.pd_step_sac_fused.argtypes = [vp, I32, I32, I32, I32, vp, vp, I32, F32, F32, F32, vp, vp, vp, I64, vp, vp, vp,
                                     vp, vp]
+    L.pd_rollout_sac.argtypes = [vp, I32, I32, I32, I32, vp, I32, F32, F32, F32, I32, I32, vp, vp, vp, vp, vp, vp, vp]
+    L.pd_rollout_sac.restype = C.c_int
     L.pd_set_tuning.argtypes = [vp, P(PdTuning)]
     L.pd_get_tuning.argtypes = [vp, P(PdTuning)]
     L.pd_rollout.argtypes = [vp, vp, I32, vp, vp]
@@ -195,4 +198,6 @@ def load(path=None):
 def check(status):
     if status != PD_OK:
         msg = load().pd_last_error().decode(errors="replace")
-        raise PdError(f"libpdenv error {status}: {msg}")
+        err = PdError(f"libpdenv error {status}: {msg}")
+        err.status = status   # (callers with a fallback tell PD_ERR_UNSUPPORTED from real failures)
+        raise err

@@ -1,7 +1,8 @@
 """Compile libpdenv.so for gfx950 in-tree (hipcc cross-compiles without a GPU).
 
 The step kernel is instantiated per (precision, phase family, wind) in 12 objects from
-csrc/kstep.hip, compiled in parallel with the host unit (pdenv.hip) and the PSO kernels
+csrc/kstep.hip (plus two RK4 units and the eight SAC rollout units, pd_rollout_sac: each its own
+object, so they build next to the others), compiled in parallel with the host unit (pdenv.hip) and the PSO kernels
 (pdpso.hip) and the SAC actor (pdsac.hip), then linked into one shared library.  Objects are rebuilt when any source is
 newer than them."""
 import concurrent.futures as cf
@@ -41,6 +42,10 @@ def units():
     for r in (0, 1):   # the non-parity RK4 kernels (pure throttle, no wind) in units of their own
         u.append((os.path.join(OBJ, f"kstep_r{r}_rk4.o"), "kstep.hip", [f"-DPD_KR={r}", "-DPD_KPH=0", "-DPD_KW=0",
                                                                         "-DPD_KRK4=1"]))
+    # the SAC rollout kernels (pd_rollout_sac: the two landing burns, 16 lanes per env), one each
+    for r, ph, w in ((r, ph, w) for r in (0, 1) for ph in (0, 1) for w in (0, 1)):
+        u.append((os.path.join(OBJ, f"kstep_r{r}_p{ph}_w{w}_roll.o"), "kstep.hip",
+                  [f"-DPD_KR={r}", f"-DPD_KPH={ph}", f"-DPD_KW={w}", "-DPD_KROLL=1"]))
     return [(o, os.path.join(CSRC, s), list(d)) for o, s, d in u]
 
 

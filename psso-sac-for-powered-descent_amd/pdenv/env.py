@@ -397,6 +397,37 @@ class PoweredDescentEnv:
         self._keep = wt                               # alive until the stream has consumed it
         return fit, steps
 
+    def rollout_sac(self, kernel, deterministic=True, reset=True, max_steps=2200, actions_out=None, rewards_out=None):
+        """Evaluation rollouts of a SAC actor on the device (pd_rollout_sac): one episode per env,
+        the actor (kernel: a pdenv.sac.ActorKernel) inside the step kernel's fused-step loop, until
+        done/truncated or max_steps; an env that ends is frozen with its terminal state, never
+        auto-reset.  reset=False: the episodes start from the handle's current state (set_state, a
+        checkpoint, a previous capped call, which it continues bit-identically).
+        actions_out [max_steps, N, A] float32 / rewards_out [max_steps, N] (handle precision), when
+        given, receive the traces: row t of env i is written only for t < steps[i].
+        Returns device tensors (returns [N], steps [N] int32, done [N] uint8, trunc_id [N] int8).
+        Needs a handle stepping 16 lanes per env and an actor of hidden width 128 or 256
+        (PdError, PD_ERR_UNSUPPORTED, otherwise: pdenv.sac.evaluate_agent then takes the per-step
+        path).  No host synchronisation."""
+        self._check_steppable()
+        a = kernel.actor
+        T = int(max_steps)
+        for t, shape, dt in ((actions_out, (T, self.n, self.action_dim), torch.float32),
+                             (rewards_out, (T, self.n), self.dtype)):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()
+                                  or t.device != self.device):
+                raise ValueError(f"trace tensor must be a contiguous {dt} {list(shape)} on {self.device}")
+        kw = dict(device=self.device)
+        ret = torch.empty(self.n, dtype=self.dtype, **kw)
+        steps = torch.empty(self.n, dtype=torch.int32, **kw)
+        done = torch.empty(self.n, dtype=torch.uint8, **kw)
+        tid = torch.empty(self.n, dtype=torch.int8, **kw)
+        L.check(self.lib.pd_rollout_sac(self.h, kernel.S, kernel.A, kernel.H, kernel.nl, kernel.ptrs(),
+                                        int(bool(deterministic)), float(a.log_std_min), float(a.log_std_max),
+                                        float(a.max_action), int(bool(reset)), T, _ptr(ret), _ptr(steps), _ptr(done),
+                                        _ptr(tid), _ptr(actions_out), _ptr(rewards_out), _stream(self.device)))
+        return ret, steps, done, tid
+
     # ------------------------------------------------------------------ checkpoint / restore
     def checkpoint(self):
         """Every per-env buffer (state, g-load window, actuators, wind, counters, aero caches)

@@ -362,3 +362,134 @@ class SACCollector:
             return full
         self.graph.replay()
         return self._finish(self._slab)
+
+
+# ---------------------------------------------------------------------------- evaluation rollouts
+class EvalResult(tuple):
+    """evaluate_agent's result.  Unpacks like the driver's pair -- `eval_reward, success_rate =
+    evaluate_agent(...)[:2]` -- and carries, as attributes, the per-env tensors `returns`, `steps`,
+    `done`, `trunc_id` (device), the `trunc_hist` dict {truncation id: episodes} and, with traces,
+    `actions` [T, N, A] float32 and `rewards` [T, N] (rows past an env's length: NaN); `fused`
+    tells which path ran."""
+
+    def __new__(cls, mean_reward, success_rate, returns, steps, done, trunc_id, trunc_hist, actions=None,
+                rewards=None, fused=False):
+        self = super().__new__(cls, (mean_reward, success_rate, returns, steps, done, trunc_id, trunc_hist,
+                                     actions, rewards))
+        self.fused = fused
+        return self
+
+    mean_reward = property(lambda s: s[0])
+    success_rate = property(lambda s: s[1])
+    returns = property(lambda s: s[2])
+    steps = property(lambda s: s[3])
+    done = property(lambda s: s[4])
+    trunc_id = property(lambda s: s[5])
+    trunc_hist = property(lambda s: s[6])
+    actions = property(lambda s: s[7])
+    rewards = property(lambda s: s[8])
+
+
+def summarize_rollout(returns, done, trunc_id):
+    """(mean_reward, success_rate, trunc_hist) of a batch of episodes, one per env: the mean of the
+    returns (np.mean(eval_rewards)), the share of episodes whose terminal step had done (the
+    driver's success_count / num_episodes, sac_pytorch_powered_descent.py:234-251; a terminal step
+    with done AND a truncation id counts as a success, as there) and {truncation id: episodes}
+    over every id that occurs (0: none).  Works on CPU and device tensors; the sums run on the
+    CPU in binary64."""
+    r = returns.detach().to("cpu", torch.float64).reshape(-1)
+    d = done.detach().to("cpu").reshape(-1) != 0
+    t = trunc_id.detach().to("cpu", torch.int64).reshape(-1)
+    n = r.numel()
+    if n == 0:
+        return float("nan"), float("nan"), {}
+    counts = torch.bincount(t.clamp_min(0))
+    hist = {int(k): int(c) for k, c in enumerate(counts.tolist()) if c}
+    return float(r.sum().item() / n), float(int(d.sum().item()) / n), hist
+
+
+def _torch_heads(actor, obs, out):
+    """[N, 2A] mean | log_std (unclamped) of an actor pd_sac_actor does not cover."""
+    f = actor.shared_net(obs)
+    return torch.cat([actor.mean(f), actor.log_std(f)], dim=1, out=out)
+
+
+@torch.no_grad()
+def _evaluate_per_step(actor, env, max_steps, deterministic, traces, check_every=16):
+    """evaluate_agent on the calls of the collection path, one step at a time: pd_step_sac_fused
+    (or the actor and pd_step_sac_ring) gives the step's float32 action and the next float32
+    observation; the handle is put back (checkpoint, stream-ordered, no sync) and pd_step of that
+    action gives the step's reward, done, truncated and trunc_id in the handle's precision -- the
+    SAC step calls return the reward only as the replay row's float32.  Bookkeeping of each env's
+    first episode in device tensors; the live count is read back every check_every steps."""
+    lib, dev, N, A, S = env.lib, env.device, env.n, env.action_dim, env.obs_dim
+    kernel = ActorKernel(actor) if ActorKernel.supported(actor) else None
+    obs = env.reset().float().contiguous()
+    kw = dict(device=dev)
+    act = torch.empty(N, A, dtype=torch.float32, **kw)
+    heads = torch.empty(N, 2 * A, dtype=torch.float32, **kw)
+    slab = torch.empty(N, 2 * S + A + 2, dtype=torch.float32, **kw)
+    blob = torch.empty(int(lib.pd_checkpoint_size(env.h)), dtype=torch.uint8, **kw)
+    ret = torch.zeros(N, dtype=env.dtype, **kw)
+    steps = torch.zeros(N, dtype=torch.int32, **kw)
+    done = torch.zeros(N, dtype=torch.uint8, **kw)
+    tid = env.episode_counters()[2].clone()
+    live = torch.ones(N, dtype=torch.bool, **kw)
+    T = int(max_steps)
+    actions = torch.full((T, N, A), float("nan"), dtype=torch.float32, **kw) if traces else None
+    rewards = torch.full((T, N), float("nan"), dtype=env.dtype, **kw) if traces else None
+    for t in range(T):
+        L.check(lib.pd_checkpoint_save(env.h, _ptr(blob), _stream(dev)))
+        skw = dict(deterministic=deterministic, ring=slab, action=act, obs32=obs)
+        if kernel is not None:
+            env.step_sac_fused(kernel.S, kernel.A, kernel.H, kernel.nl, kernel.ptrs(), actor.log_std_min,
+                               actor.log_std_max, actor.max_action, **skw)
+        else:
+            env.step_sac_ring(_torch_heads(actor, obs, heads), actor.log_std_min, actor.log_std_max,
+                              actor.max_action, **skw)
+        L.check(lib.pd_checkpoint_load(env.h, _ptr(blob), _stream(dev)))
+        env.step_raw_noflush(act)
+        r = env.reward_buf
+        ret = torch.where(live, ret + r, ret)
+        steps += live
+        if traces:
+            actions[t] = torch.where(live[:, None], act, actions[t])
+            rewards[t] = torch.where(live, r, rewards[t])
+        ended = live & ((env.done_buf | env.trunc_buf) != 0)
+        done = torch.where(ended, env.done_buf, done)
+        tid = torch.where(live, env.trunc_id_buf, tid)
+        live = live & ~ended
+        if (t + 1) % check_every == 0 and not bool(live.any()):
+            break
+    return ret, steps, done, tid, actions, rewards
+
+
+@torch.no_grad()
+def evaluate_agent(actor, env, max_steps=2200, deterministic=True, fused=True, traces=False):
+    """The SAC driver's evaluate_agent (sac_pytorch_powered_descent.py:234-251) -- and, with
+    traces=True, the loop of visualize_trajectory (:354-376) -- over the handle's N envs, one env
+    one episode: every env is reset and driven by actor.sample(state, deterministic) until done or
+    truncated (or max_steps).  Returns an EvalResult: (mean_reward, success_rate, ...) with
+    success_rate the share of episodes whose terminal step had done.
+    fused=True: ONE call, pd_rollout_sac -- the actor inside the step kernel's fused-step loop, no
+    host synchronisation -- where the handle steps 16 lanes per env and the actor fits
+    (ActorKernel.supported, hidden 128 or 256); otherwise, and with fused=False, the per-step path
+    on pd_step_sac_fused / pd_step_sac_ring.  Both paths return the same values."""
+    T = int(max_steps)
+    out = None
+    if fused and ActorKernel.supported(actor) and actor.mean.in_features != 512:
+        kw = dict(device=env.device)
+        actions = torch.full((T, env.n, env.action_dim), float("nan"), dtype=torch.float32, **kw) if traces else None
+        rewards = torch.full((T, env.n), float("nan"), dtype=env.dtype, **kw) if traces else None
+        try:
+            out = env.rollout_sac(ActorKernel(actor), deterministic=deterministic, reset=True, max_steps=T,
+                                  actions_out=actions, rewards_out=rewards) + (actions, rewards)
+        except L.PdError as err:   # (a handle the kernel refuses: not 16 lanes per env)
+            if getattr(err, "status", None) != L.PD_ERR_UNSUPPORTED:
+                raise
+    used_fused = out is not None
+    if out is None:
+        out = _evaluate_per_step(actor, env, T, deterministic, traces)
+    ret, steps, done, tid, actions, rewards = out
+    mean_reward, success_rate, hist = summarize_rollout(ret, done, tid)
+    return EvalResult(mean_reward, success_rate, ret, steps, done, tid, hist, actions, rewards, fused=used_fused)

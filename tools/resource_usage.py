@@ -3,7 +3,8 @@
 (hipcc -Rpass-analysis=kernel-resource-usage on each kstep translation unit of pdenv/build.py).
   python tools/resource_usage.py [out.txt]
 Prints one row per kernel: precision, phase family, rtd, wind, lanes per env, policy, RK4,
-counting, SAC; VGPRs, spilled VGPRs, scratch bytes per lane, LDS bytes, waves per SIMD."""
+counting, SAC, the SAC rollout; VGPRs, spilled VGPRs, spilled SGPRs, scratch bytes per lane, LDS
+bytes, waves per SIMD."""
 import concurrent.futures as cf
 import os
 import re
@@ -14,7 +15,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "psso-sac-for-powered-descent_amd"))
 from pdenv import build as b  # noqa: E402
 
-FIELDS = {"VGPRs": "vgpr", "VGPRs Spill": "vgpr_spill", "ScratchSize [bytes/lane]": "scratch",
+FIELDS = {"VGPRs": "vgpr", "VGPRs Spill": "vgpr_spill", "SGPRs Spill": "sgpr_spill", "ScratchSize [bytes/lane]": "scratch",
           "LDS Size [bytes/block]": "lds", "Occupancy [waves/SIMD]": "waves"}
 
 
@@ -36,25 +37,26 @@ def unit_report(job):
 
 
 def decode(name):
-    m = re.match(r"_ZN2pd6k_stepI([df])Li(\d+)ELi(\d+)ELb(\d)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)E", name)
+    m = re.match(r"_ZN2pd6k_stepI([df])Li(\d+)ELi(\d+)ELb(\d)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)ELb(\d)E", name)
     if not m:
         return None
-    r, ph, rt, w, lpe, pol, rk, cnt, sac = m.groups()
-    return (("f64" if r == "d" else "f32"), int(ph), int(rt), int(w), int(lpe), int(pol), int(rk), int(cnt), int(sac))
+    r, ph, rt, w, lpe, pol, rk, cnt, sac, roll = m.groups()
+    return (("f64" if r == "d" else "f32"), int(ph), int(rt), int(w), int(lpe), int(pol), int(rk), int(cnt), int(sac),
+            int(roll))
 
 
 def main():
     jobs = [u for u in b.units() if "kstep" in u[0]]
     with cf.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as ex:
         allrows = [r for rows in ex.map(unit_report, jobs) for r in rows]
-    out = ["prec phase rtd wind lpe pol rk4 cnt sac | vgpr spill scratch lds waves"]
+    out = ["prec phase rtd wind lpe pol rk4 cnt sac roll | vgpr spill sgpr_spill scratch lds waves"]
     seen = set()
     for r in sorted(allrows, key=lambda r: decode(r["name"]) or ()):
         k = decode(r["name"])
         if k is None or k in seen:
             continue
         seen.add(k)
-        out.append(" ".join(str(v) for v in k) + f" | {r.get('vgpr')} {r.get('vgpr_spill')} {r.get('scratch')} "
+        out.append(" ".join(str(v) for v in k) + f" | {r.get('vgpr')} {r.get('vgpr_spill')} {r.get('sgpr_spill')} {r.get('scratch')} "
                    f"{r.get('lds')} {r.get('waves')}")
     txt = "\n".join(out)
     print(txt)
