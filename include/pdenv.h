@@ -74,13 +74,14 @@ typedef enum { PD_F64 = 0, PD_F32 = 1 } pd_precision;
  * (orc_physics, ORC_INTEG_RK4), not against the reference. */
 typedef enum { PD_INTEG_REFERENCE = 0, PD_INTEG_RK4 = 1 } pd_integrator;
 /* pd_config.table_flags: how the aero and atmosphere lookups are served (results agree within the
- * tolerances of DESIGN.md s4/s8; the cell-piece and fine-index switches give the same bits as
+ * tolerances of DESIGN.md s4/s8; the cell-piece, fine-index and carry switches give the same bits as
  * their default, which the GPU tests check).  0 = the defaults. */
 typedef enum {
     PD_TABLES_NO_CELL_PIECES = 1,   /* interior C_D/C_L queries by payload sums, not cell pieces */
     PD_TABLES_NO_FINE_INDEX = 2,    /* cell pieces reached through the cell / sub-cell records only */
     PD_TABLES_EXACT_ATMOSPHERE = 4, /* the ISA closed form on the device, never the tabulated pieces */
-    PD_TABLES_VERBOSE = 8           /* print the table builders' statistics to stderr at create */
+    PD_TABLES_VERBOSE = 8,          /* print the table builders' statistics to stderr at create */
+    PD_TABLES_NO_CARRY = 16         /* the step kernel's searches take no carried interval as a guess */
 } pd_table_flags;
 
 /* One neighbourhood-aero table: scatter points grouped by AoA column, Mach-sorted inside. */
@@ -487,10 +488,13 @@ pd_status pd_atmosphere(pd_env* env, const void* altitude, void* out, int64_t n,
  * from a Taylor piece, 37 by the balanced chunk sums, 38 missed (device solve), 39 balanced-sum
  * rounds, 40 interior queries in a refined grid cell, 41 ... in a sub-cell split by a bisector,
  * 42 / 43 wave sub-steps with at least one such query, 44 queries evaluated from a cell piece,
- * 45 wave sub-steps holding both clamped-line and interior queries.  Host sync. */
-#define PD_N_STATS 48
+ * 45 wave sub-steps holding both clamped-line and interior queries; the carried search intervals,
+ * per search a pair of wave sub-step counts -- every lane's carried guess held / the search ran:
+ * 46 / 47 wind profile knots, 48 / 49 grid-fin C_a knots.
+ * Host sync. */
+#define PD_N_STATS 64
 pd_status pd_stats(pd_env* env, int64_t* out, int32_t n);
-/* Workload counting (pd_stats words 32-45) on (enable != 0) or off (the default) for the handle's
+/* Workload counting (pd_stats words 32-49) on (enable != 0) or off (the default) for the handle's
  * following step launches with 2 lanes per env (the default above 16 384 envs; other launches
  * count nothing).  A diagnostic: on, the launches run a counting instantiation of the step kernel
  * (a ballot and an LDS add per counter per sub-step, a few per cent slower); off, the product

@@ -450,11 +450,9 @@ __device__ __forceinline__ void obs_write(DP<R>& P, int kind, const R* s, R* out
 // scipy interp1d._call_linear with fill_value='extrapolate' (grid_fin_aerodynamics.py:7-18)
 // (slope: the intervals' slopes (y[i] - y[i-1]) / (x[i] - x[i-1]) at index i, tabulated with the
 // same operation, or nullptr: computed here)
+// (the search, shared with grid_fin_ca_carry: the lower bound of mach over sx[0..n), before its clamp)
 template <typename R>
-__device__ __forceinline__ R grid_fin_ca(DP<R>& P, const R* sx, const R* sy, R mach, const uint16_t* lb = nullptr,
-                                         const R* slope = nullptr) {
-    if (mach < P.ca_min_mach) return P.ca_min_val;
-    int n = P.ca_n;
+__device__ __forceinline__ int grid_fin_ca_search(const R* sx, int n, R mach, const uint16_t* lb) {
     int lo = 0, hi = n;                       // lower_bound: first x >= mach
     if (lb != nullptr && mach >= R(0) && mach < R(10)) {   // within the Mach bucket's index range
         int b = (int)(mach * R(6.4));
@@ -463,24 +461,109 @@ __device__ __forceinline__ R grid_fin_ca(DP<R>& P, const R* sx, const R* sy, R m
         lo = (int)(rg & 0xffu); hi = (int)(rg >> 8);
     }
     while (lo < hi) { int mid = (lo + hi) >> 1; if (sx[mid] < mach) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+template <typename R>
+__device__ __forceinline__ R grid_fin_ca(DP<R>& P, const R* sx, const R* sy, R mach, const uint16_t* lb = nullptr,
+                                         const R* slope = nullptr) {
+    if (mach < P.ca_min_mach) return P.ca_min_val;
+    int n = P.ca_n;
+    const int lo = grid_fin_ca_search<R>(sx, n, mach, lb);
     int idx = lo < 1 ? 1 : (lo > n - 1 ? n - 1 : lo);
     R xl = sx[idx - 1], yl = sy[idx - 1];
     const R sl = slope ? slope[idx] : (sy[idx] - yl) / (sx[idx] - xl);
     return sl * (mach - xl) + yl;
 }
 
+// The carried search intervals (one word per lane, beside its RbfCache): the last answer of the
+// wind profile search (the knot j) and of the grid-fin C_a search (the lower bound before its
+// clamp).  Each is only a guess: the search's own postcondition is checked on it, a guess that
+// passes is the index the search would return (the same arithmetic, the same bits) and one that
+// fails runs the search.  So nothing invalidates the word: a reset, a restore or another profile
+// only falls back.  (The clamped-line breakpoint search takes no guess: with one the c3 kernel
+// measured 2-4 % slower, a wave's line lanes all hold in 4-9 % of its sub-steps; DESIGN.md s6,
+// tools/experiments/line_carry.patch.)
+// PD_CARRY (experiment builds): bit 0 the wind search takes a guess, bit 1 the grid-fin search,
+// bit 2: the next step's action is requested one step ahead (pd_step_impl.h)
+#ifndef PD_CARRY
+#define PD_CARRY 7
+#endif
+constexpr uint32_t kCarryWindShift = 0, kCarryWindMask = 0xfu, kCarryFinShift = 4, kCarryFinMask = 0xffu;
+constexpr uint32_t kCarryNone = 0xffffffffu;   // every field's "none" (no interval has that index)
+__device__ __forceinline__ uint32_t carry_get(uint32_t cw, uint32_t shift, uint32_t mask) { return (cw >> shift) & mask; }
+__device__ __forceinline__ uint32_t carry_set(uint32_t cw, uint32_t shift, uint32_t mask, uint32_t v) {
+    return (cw & ~(mask << shift)) | ((v & mask) << shift);   // (-1 packs as the field's "none")
+}
+// how a carried search went on this lane (for the counters): not reached, guess held, search ran
+enum CarryRes { kCarrySkip = 0, kCarryHit = 1, kCarrySearch = 2 };
+
+// grid_fin_ca with the carried lower bound g (0..n; kCarryFinMask: none) as a guess: lo = g is the
+// search's answer iff (g == 0 || sx[g-1] < mach) && (g == n || sx[g] >= mach); the reads of the
+// check and of the evaluation are independent of each other
+template <typename R>
+__device__ __forceinline__ R grid_fin_ca_carry(DP<R>& P, const R* sx, const R* sy, R mach, const uint16_t* lb,
+                                               const R* slope, uint32_t& g, int& res) {
+    res = kCarrySkip;
+    if (mach < P.ca_min_mach) return P.ca_min_val;
+    const int n = P.ca_n;
+    bool ok = g != kCarryFinMask && (int)g <= n;
+    int lo = ok ? (int)g : 0;
+    int idx = lo < 1 ? 1 : (lo > n - 1 ? n - 1 : lo);
+    const R xa = sx[lo > 0 ? lo - 1 : 0], xb = sx[lo < n ? lo : n - 1];
+    R xl = sx[idx - 1], yl = sy[idx - 1];
+    R sl = slope[idx];
+    ok = ok && (lo == 0 || xa < mach) && (lo == n || xb >= mach);
+    res = ok ? kCarryHit : kCarrySearch;
+    if (!ok) {
+        lo = grid_fin_ca_search<R>(sx, n, mach, lb);
+        idx = lo < 1 ? 1 : (lo > n - 1 ? n - 1 : lo);
+        xl = sx[idx - 1]; yl = sy[idx - 1];
+        sl = slope[idx];
+    }
+    g = (uint32_t)lo;
+    return sl * (mach - xl) + yl;
+}
+
 // np.interp for an in-range query (numpy compiled_base.c arr_interp)
 // (slope: (y[j + 1] - y[j]) / (x[j + 1] - x[j]) tabulated at index j, or nullptr: computed here)
+// (the in-range search, shared with np_interp_carry: the knot j with x[j] <= v < x[j + 1])
+template <typename R>
+__device__ __forceinline__ int np_interp_search(const R* x, int n, R v) {
+    int lo = 0, hi = n;                       // upper_bound: first x > v
+    while (lo < hi) { int mid = (lo + hi) >> 1; if (x[mid] <= v) lo = mid + 1; else hi = mid; }
+    return lo - 1;
+}
 template <typename R>
 __device__ __forceinline__ R np_interp(const R* x, const R* y, int n, R v, const R* slope = nullptr) {
     if (v < x[0]) return y[0];
     if (v >= x[n - 1]) return y[n - 1];
-    int lo = 0, hi = n;                       // upper_bound: first x > v
-    while (lo < hi) { int mid = (lo + hi) >> 1; if (x[mid] <= v) lo = mid + 1; else hi = mid; }
-    int j = lo - 1;
+    int j = np_interp_search<R>(x, n, v);
     if (x[j] == v) return y[j];
     const R sl = slope ? slope[j] : (y[j + 1] - y[j]) / (x[j + 1] - x[j]);
     return sl * (v - x[j]) + y[j];
+}
+
+// np_interp (no tabulated slopes) with the carried knot j (0..n-2; kCarryWindMask: none) as a
+// guess: x[j] <= v < x[j+1] with j < n - 1 is the in-range search's answer (and implies that neither
+// early-out applies), so a guess that passes reads neither x[0] nor x[n-1]
+template <typename R>
+__device__ __forceinline__ R np_interp_carry(const R* x, const R* y, int n, R v, uint32_t& g, int& res) {
+    bool ok = g != kCarryWindMask && (int)g < n - 1;
+    int j = ok ? (int)g : 0;
+    R x0 = x[j], x1 = x[j + 1], y0 = y[j], y1 = y[j + 1];   // (rows of 16 knots: j + 1 <= 15)
+    ok = ok && x0 <= v && v < x1;
+    res = ok ? kCarryHit : kCarrySearch;
+    if (!ok) {
+        res = kCarrySkip;
+        if (v < x[0]) return y[0];
+        if (v >= x[n - 1]) return y[n - 1];
+        res = kCarrySearch;
+        j = np_interp_search<R>(x, n, v);
+        x0 = x[j]; y0 = y[j]; x1 = x[j + 1]; y1 = y[j + 1];
+        g = (uint32_t)j;
+    }
+    if (x0 == v) return y0;
+    return (y1 - y0) / (x1 - x0) * (v - x0) + y0;
 }
 
 // grid_fin_aerodynamics.py:21-46: cn_alpha(M) * degrees(alpha)

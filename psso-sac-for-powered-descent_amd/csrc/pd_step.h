@@ -64,7 +64,7 @@ struct GridBisect {
     int piece_a, piece_b;   // each side's cell piece (binary64 handles; -1: none)
 };
 constexpr int kGridSub = 8;   // sub-cells per refined cell side
-constexpr int kStats = 48;            // pend.stats words (see Stat)
+constexpr int kStats = 64;            // pend.stats words (see Stat)
 
 // pend.stats[] words
 enum Stat {
@@ -88,7 +88,11 @@ enum Stat {
     kStWBisect = kStWork + 11,   // wave sub-steps with at least one bisector query
     kStQCell = kStWork + 12,     // LPE 2 queries evaluated from a cell piece
     kStWMixed = kStWork + 13,    // wave sub-steps holding both clamped-line and interior queries
-    kNWork = 14
+    // the carried search intervals (pd_physics.h kCarryNone), per search: wave sub-steps in which the
+    // guess of every lane that reached the search held, and wave sub-steps in which the search ran
+    kStCWindHit = kStWork + 14, kStCWindSearch = kStWork + 15,   // wind profile knots
+    kStCFinHit = kStWork + 16, kStCFinSearch = kStWork + 17,     // grid-fin C_a knots
+    kNWork = 18
 };
 
 // Per-wave workload counts in LDS (nullptr: counting off, the launch pays one scalar branch per
@@ -103,6 +107,15 @@ struct WaveCount {
     }
     __device__ __forceinline__ void add_n(int k, uint32_t v) {
         if (w && __lane_id() == 0) w[k] += v;
+    }
+    // a carried search of the converged wave: word k counts the wave if every active lane that
+    // reached the search passed its guess, word k + 1 if the search ran for some active lane (the
+    // caller masks both with the lane's being live)
+    __device__ __forceinline__ void add_carry(int k, bool hit, bool search) {
+        if (w) {
+            const bool s = __ballot(search) != 0ull, h = __ballot(hit) != 0ull;
+            if (__lane_id() == 0) { w[k] += (uint32_t)(h && !s); w[k + 1] += (uint32_t)s; }
+        }
     }
 };
 
@@ -227,6 +240,7 @@ __device__ void insert_pending(unsigned long long* count, const unsigned long lo
     *count = 0;
 }
 
+constexpr int kArgCount = 1, kArgNoCarry = 2;   // StepArgs::count_work bits
 template <typename R> struct StepArgs {
     uint64_t P;                      // const DevParams<R>* (read through a constant-AS view)
     EnvBufs<R> b;
@@ -254,7 +268,9 @@ template <typename R> struct StepArgs {
     double dt_aux;                   // physics dt of phases 2..6 (compile_physics(dt, phase))
     int rtd_none;                    // PD_RTD_NONE: physics stepping only (reward/done/trunc 0)
     int n_fused;                     // env-steps per launch (actions/outputs: [n_fused][N] rows)
-    int count_work;                  // workload counters on (pd_count_work; diagnostic launches)
+    // bit 0 (kArgCount): workload counters on (pd_count_work; diagnostic launches); bit 1
+    // (kArgNoCarry): PD_TABLES_NO_CARRY, the searches take no carried guess
+    int count_work;
     // pd_step_sac (single-step launches): the action sampled from the actor's heads in the kernel,
     // tanh(mean + exp(clamp(log_std, lo, hi)) eps) max (eps NULL: tanh(mean) max), and float32
     // outputs: the action, the transition row [N][2S + A + 2] and the next observation [N][S]

@@ -1025,9 +1025,9 @@ __device__ __forceinline__ void actor_forward(const float* __restrict__ W, int64
 // ---------------------------------------------------------------- LDS of one step workgroup
 // (the tables every workgroup stages come first: StepStatic, pd_step.h, copied from the handle's
 // image of it)
-template <typename R, bool WIND, int EPB, bool BAL = false> struct StepLds : StepStatic<R, WIND> {
+template <typename R, bool WIND, int EPB, bool BAL = false, bool CNT = false> struct StepLds : StepStatic<R, WIND> {
     R gwin[10][EPB];              // the g-load ring of each env of the workgroup (register-resident launches)
-    uint32_t work[kStepBlock / 64][kNWork];   // per-wave workload counts (counting launches)
+    uint32_t work[kStepBlock / 64][CNT ? kNWork : 1];   // per-wave workload counts (the counting instantiation)
     double wnx[WIND ? 2 : 1][WIND ? kStepBlock : 1];   // each lane's gust normals of the next (odd) sub-step
     BalLds<R> bal[BAL ? kStepBlock / 64 : 1];   // LPE 2: balanced-sum space per wave
     TabView<R> tdesc[2];          // each table's view, staged once: a lane's table is per lane
@@ -1094,7 +1094,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
     static_assert(!ROLL || (SAC && LPE == 16 && !POL && !RK4 && !CNT && RTD == 0 && PHASE <= 1),
                   "ROLL: the SAC kernel of the RL landing burns at 16 lanes per env");
     constexpr int EPB = kStepBlock / LPE;   // envs per workgroup
-    __shared__ StepLds<R, WIND, EPB, LPE == 2> L;
+    __shared__ StepLds<R, WIND, EPB, LPE == 2, CNT> L;
 #ifdef PD_STAMP
     unsigned long long acc_[17] = {};   // [7], [8]: rbf2 lookup, evaluation; [9..12] lookup parts; [13..16] post-aero parts
 #endif
@@ -1164,6 +1164,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
     // prologue and the table staging, whose latencies then overlap it
     EnvRegs<R> e;
     RbfCache<R> cA, cB;   // LPE 1: A = C_D, B = C_L; LPE >= 2: A = own table
+    uint32_t carry;       // the lane's carried search intervals (pd_physics.h kCarryNone; not stored with the env)
     auto load_env = [&]() {
         DP<R>& P = *params<R>(a.P);
 #pragma unroll
@@ -1193,6 +1194,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
         e.tid = valid ? (int)ldv(a.b.tid, ui) : 0;
         cA.key = valid ? ldv(a.b.key + (my_table) * N, ui) : (my_table ? P.init_key_cl : P.init_key_cd);
         cA.slot = valid ? ldv(a.b.slot + (my_table) * N, ui) : -1;
+        carry = kCarryNone;   // (a launch's first sub-step searches)
         if constexpr (LPE == 1) { cB.key = valid ? ldv(a.b.key + N, ui) : P.init_key_cl; cB.slot = valid ? ldv(a.b.slot + N, ui) : -1; }
         else { cB.key = 0; cB.slot = -1; }
     };
@@ -1248,7 +1250,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
             if (t < kImg) ((V4*)static_cast<StepStatic<R, WIND>*>(&L))[t] = stg[k];
             else if (t < kImg + kLog) ((V4*)s_logtab)[t - kImg] = stg[k];
         }
-        if (threadIdx.x < (kStepBlock / 64) * kNWork) (&L.work[0][0])[threadIdx.x] = 0u;
+        if constexpr (CNT) { if (threadIdx.x < (kStepBlock / 64) * kNWork) (&L.work[0][0])[threadIdx.x] = 0u; }
         if (threadIdx.x < 2) L.tdesc[threadIdx.x] = tab_view<R>(P, L.tab, (int)threadIdx.x);
     }
     __syncthreads();
@@ -1267,6 +1269,23 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
     // one call of rocket_physics_fcn at dt, actuators at the same dt (rockets_physics.py:728-997)
     static_assert(!RK4 || (PHASE == 0 && !WIND && !POL), "RK4: pure throttle, no wind, no policy");
     constexpr int NSUB = RK4 ? 40 : (PHASE == 2 ? 1 : 4);
+    // the carried search intervals (pd_physics.h kCarryNone) and the action row requested a step
+    // ahead, in the instantiations that keep their registers with them: not the binary32 kernels
+    // (168 registers, the edge of three waves per SIMD: the carried word takes the 4- and 8-lane
+    // ones to two waves), nor the 16-lane RK4 kernel, which already spills, nor the SAC kernels,
+    // whose landing-burn wind instantiations spill.  PD_CARRY_WIDE=1 (experiment builds) lifts
+    // these limits: the compiler's report of that build is profiles/carry_resource_usage_wide.txt,
+    // next to the product's profiles/carry_resource_usage.txt
+#ifndef PD_CARRY_WIDE
+#define PD_CARRY_WIDE 0
+#endif
+    constexpr bool kSpills = RK4 && LPE == 16;
+    constexpr bool kCarry = (PD_CARRY & 3) != 0 && (PD_CARRY_WIDE || (sizeof(R) == 8 && !kSpills && !SAC));
+    // (plain-action kernels only -- no policy, no SAC actor -- and of those the one-component rows
+    // of the binary64 pure-throttle kernels: the other phases' wider rows and the binary32
+    // kernels are in the same two reports)
+    constexpr bool kActAhead = (PD_CARRY & 4) != 0 && !POL && !SAC &&
+                               (PD_CARRY_WIDE || (PHASE == 0 && sizeof(R) == 8 && !kSpills));
     // LPE != 2: pieces for the trusted queries (rbf) where they fit the register file without
     // spilling (no wind, no RK4, not the landing-burn SAC kernel): c2, c5, the policy sweep
     // the tabulated atmosphere where it pays: binary32 handles and the windless kernels (c2, c4,
@@ -1367,6 +1386,34 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
         if constexpr (sizeof(R) == 8) return e.s[k];
         else return xs[k];
     };
+    // kActAhead: the action row of step f + 1 is requested in step f, once its last sub-step has
+    // consumed its table records (vector loads return in order: ahead of a lookup's loads the
+    // request would hold them back), and used at the head of step f + 1 -- the row is streamed
+    // data, a miss to HBM every step; the raw words of a binary32 (w0) or binary64 (w0, w1) row.
+    // No request is made for a row past nf - 1
+    uint32_t an0[kActAhead ? A : 1], an1[kActAhead ? A : 1];
+    auto act_request = [&](int fr) {
+        if constexpr (kActAhead) {
+            SA<R>& a = kargs<R>();
+            const size_t fo = (size_t)fr * (size_t)N;
+            if (a.act_f64) {
+#pragma unroll
+                for (int k = 0; k < A; ++k) if (k < AD) {
+                    const unsigned long long w = (unsigned long long)__double_as_longlong(
+                        ldv((const double*)a.actions + fo * AD + k, ui * AD));
+                    an0[k] = (uint32_t)w; an1[k] = (uint32_t)(w >> 32);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < A; ++k) if (k < AD) an0[k] = __float_as_uint(ldv((const float*)a.actions + fo * AD + k, ui * AD));
+            }
+        }
+    };
+    if constexpr (kActAhead) {
+#pragma unroll
+        for (int k = 0; k < A; ++k) { an0[k] = 0u; an1[k] = 0u; }
+        if (nf > 0) act_request(0);
+    }
 #pragma unroll 1
     for (int f = 0; f < nf; ++f) {
     SA<R>& a = kargs<R>();
@@ -1463,6 +1510,12 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
                     ev(a.roll_act + (size_t)(a.roll_t0 + f) * (size_t)N * (size_t)AD + k, ui * AD) = uf[k];
             }
         }
+    } else if constexpr (kActAhead) {
+#pragma unroll
+        for (int k = 0; k < A; ++k) if (k < AD) {
+            if (a.act_f64) ud[k] = __longlong_as_double((long long)(((unsigned long long)an1[k] << 32) | an0[k]));
+            else uf[k] = __uint_as_float(an0[k]);
+        }
     } else if (a.act_f64) {
 #pragma unroll
         for (int k = 0; k < A; ++k) if (k < AD) ud[k] = ldv((const double*)a.actions + fo * AD + k, ui * AD);
@@ -1521,6 +1574,8 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
         SA<R>& a = kargs<R>();
         DP<R>& P = *params<R>(a.P);
         const bool tap_sub = tap && sub == NSUB - 1;
+        // PD_TABLES_NO_CARRY: every guess fails
+        if constexpr (kCarry) { if (a.count_work & kArgNoCarry) carry = kCarryNone; }
         RS x = SV(0), y = SV(1), vx = SV(2), vy = SV(3), th = SV(4), thd = SV(5), ga = SV(6), al = SV(7);
         RS m = SV(8), mp = SV(9);
         if constexpr (WIND) wc.add(kStGust - kStWork, role == 0 && live && a.stochastic && y < P.vk_y_threshold);
@@ -1548,7 +1603,15 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
                 const R* wsp = L.wsp + e.prof * 16;
                 R km = PD_DIVC(R, (R)y, 1000);
                 int wn = P.wind_n[e.prof];
-                ug = np_interp<R>(walt, wsp, wn, km);
+                if constexpr (kCarry && (PD_CARRY & 1)) {
+                    uint32_t wj = carry_get(carry, kCarryWindShift, kCarryWindMask);
+                    int wres;
+                    ug = np_interp_carry<R>(walt, wsp, wn, km, wj, wres);
+                    carry = carry_set(carry, kCarryWindShift, kCarryWindMask, wj);
+                    wc.add_carry(kStCWindHit - kStWork, live && wres == kCarryHit, live && wres == kCarrySearch);
+                } else {
+                    ug = np_interp<R>(walt, wsp, wn, km);
+                }
                 const bool gust = y < P.vk_y_threshold && a.stochastic;
                 if (gust) {
                     double w0 = 0.0, w1 = 0.0;
@@ -1682,7 +1745,16 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
 #endif
         R T_full = P.T_e + (P.p_e - patm) * P.A_e;
         R qS = q * P.S_gf;
-        R Ca = grid_fin_ca<R>(P, L.gf, L.gf + 64, mach, L.ca_lb, L.gfs);
+        R Ca;
+        if constexpr (kCarry && (PD_CARRY & 2)) {
+            uint32_t fg = carry_get(carry, kCarryFinShift, kCarryFinMask);
+            int fres;
+            Ca = grid_fin_ca_carry<R>(P, L.gf, L.gf + 64, mach, L.ca_lb, L.gfs, fg, fres);
+            carry = carry_set(carry, kCarryFinShift, kCarryFinMask, fg);
+            wc.add_carry(kStCFinHit - kStWork, live && fres == kCarryHit, live && fres == kCarrySearch);
+        } else {
+            Ca = grid_fin_ca<R>(P, L.gf, L.gf + 64, mach, L.ca_lb, L.gfs);
+        }
         R cfp, cfperp, cm, mdot_dt, md_info, thr_info;
         // info of the grid-fin ACS (acs_model.py:62-86): deflections, C_n of both fins, forces
         R i_dl = R(0), i_dr = R(0), i_cnl = R(0), i_cnr = R(0), i_gfperp = R(0), i_gfpar = R(0), i_gfm = R(0);
@@ -1932,6 +2004,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
         PD_ACC(4, t_subend - t_aero1);
     }
     if (nan_hit && role == 0 && live) atomicAdd(&a.pend.stats[kStNan], 1ull);
+    if constexpr (kActAhead) { if (f + 1 < nf) act_request(f + 1); }
     if constexpr (sizeof(R) == 4) {   // the env-step's state, rounded once
 #pragma unroll
         for (int k = 0; k < 11; ++k) e.s[k] = (R)xs[k];
@@ -2333,7 +2406,7 @@ template <typename R, int PH, int RT, bool W, int LPE, bool RK> void launch_step
     // prologue (sac_mlp.H, pd_step_sac_fused: sac_mean is then NULL and a.actions too)
     const bool sac = a.sac_mean != nullptr || a.sac_mlp.H != 0;
     if constexpr (LPE == 2 && !RK) {
-        if (a.count_work && !sac) {
+        if ((a.count_work & kArgCount) && !sac) {
             hipLaunchKernelGGL((k_step<R, PH, RT, W, LPE, 0, RK, true>), dim3(grid), dim3(kStepBlock), 0, s, a);
             return;
         }

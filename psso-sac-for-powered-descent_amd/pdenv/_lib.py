@@ -82,7 +82,7 @@ class PdConfig(C.Structure):
 
 
 # pd_table_flags
-TABLES_NO_CELL_PIECES, TABLES_NO_FINE_INDEX, TABLES_EXACT_ATMOSPHERE, TABLES_VERBOSE = 1, 2, 4, 8
+TABLES_NO_CELL_PIECES, TABLES_NO_FINE_INDEX, TABLES_EXACT_ATMOSPHERE, TABLES_VERBOSE, TABLES_NO_CARRY = 1, 2, 4, 8, 16
 
 
 class PdTuning(C.Structure):

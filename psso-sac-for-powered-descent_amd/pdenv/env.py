@@ -500,13 +500,16 @@ class PoweredDescentEnv:
 
     WORK_COUNTERS = ("gust_substeps", "resets", "q_line", "q_verified", "q_taylor", "q_balanced", "q_miss",
                      "balanced_rounds", "q_refined", "q_bisect", "wave_substeps_refined", "wave_substeps_bisect",
-                     "q_cell", "wave_substeps_mixed")
+                     "q_cell", "wave_substeps_mixed",
+                     # the carried search intervals: wave sub-steps in which every lane's guess held /
+                     # in which the search ran, per search
+                     "carry_wind_hit", "carry_wind_search", "carry_fin_hit", "carry_fin_search")
 
     def stats(self):
         """Device statistics words (pd_stats): misses, NaN events, table entries, dropped queue
         entries, and the step kernel's workload counters since create (include/pdenv.h pd_stats)."""
-        v = (L.I64 * 48)()
-        L.check(self.lib.pd_stats(self.h, v, 48))
+        v = (L.I64 * 64)()
+        L.check(self.lib.pd_stats(self.h, v, 64))
         out = {"rbf_misses": v[0], "nan_events": v[1], "table_entries_cd": v[2], "table_entries_cl": v[3],
                "miss_queue_dropped": v[16]}
         out.update({k: v[32 + j] for j, k in enumerate(self.WORK_COUNTERS)})
