@@ -2,9 +2,11 @@
 
 The step kernel is instantiated per (precision, phase family, wind) in 12 objects from
 csrc/kstep.hip (plus two RK4 units and the eight SAC rollout units, pd_rollout_sac: each its own
-object, so they build next to the others), compiled in parallel with the host unit (pdenv.hip) and the PSO kernels
-(pdpso.hip) and the SAC actor (pdsac.hip), then linked into one shared library.  Objects are rebuilt when any source is
-newer than them."""
+object, so they build next to the others), compiled in parallel with the two host units -- the
+handle and C ABI (pdenv.hip) and the host table builder (pd_tables.hip: host code only, with the
+same flags, on which the tables' bits depend) -- and the PSO kernels (pdpso.hip) and the SAC actor
+(pdsac.hip), then linked into one shared library.  Objects are rebuilt when any source is newer
+than them."""
 import concurrent.futures as cf
 import os
 import subprocess
@@ -22,6 +24,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # polynomials out of the sub-step loop into VGPRs (>60 VGPRs, a 2x occupancy loss).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-Wno-unused-result", "-mllvm", "-disable-machine-licm"]
+HOST_UNITS = ("pdenv", "pd_tables")
 KSTEP = [(r, ph, w) for r in (0, 1) for ph in (0, 1, 2) for w in (0, 1)]
 
 
@@ -34,8 +37,7 @@ KSTEP_FLAGS = {(0, 0, 1): ["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"]
 
 def units():
     """(object path, source, defines) of every translation unit."""
-    u = [(os.path.join(OBJ, "pdenv.o"), "pdenv.hip", []), (os.path.join(OBJ, "pdpso.o"), "pdpso.hip", []),
-         (os.path.join(OBJ, "pdsac.o"), "pdsac.hip", [])]
+    u = [(os.path.join(OBJ, f"{n}.o"), f"{n}.hip", []) for n in HOST_UNITS + ("pdpso", "pdsac")]
     for r, ph, w in KSTEP:
         u.append((os.path.join(OBJ, f"kstep_r{r}_p{ph}_w{w}.o"), "kstep.hip",
                   [f"-DPD_KR={r}", f"-DPD_KPH={ph}", f"-DPD_KW={w}"] + KSTEP_FLAGS.get((r, ph, w), [])))
@@ -102,7 +104,7 @@ def build_variant(name, defines, unit=(0, 0, 1), patch=None, host=False):
     family, wind; default the c3 one) compiled with extra `defines` -- and, given `patch` (a
     unified diff against csrc/, e.g. tools/experiments/*.patch), from a patched copy of the
     sources, so that experiments stay out of the product source -- the other objects shared with
-    the main build (which must be current); host=True also compiles the host unit (pdenv.hip)
+    the main build (which must be current); host=True also compiles the host units (HOST_UNITS)
     with them.  Returns the library path."""
     import shutil
     import tempfile
@@ -121,16 +123,16 @@ def build_variant(name, defines, unit=(0, 0, 1), patch=None, host=False):
         subprocess.run(["patch", "-s", "-t", "-p2", "-d", os.path.join(tmp, "p", "csrc"), "-i", os.path.abspath(patch)],
                        check=True)
         src = os.path.join(tmp, "p", "csrc", "kstep.hip")
-    hobj = os.path.join(odir, "pdenv.o")
+    hobjs = {f"{n}.o": os.path.join(odir, f"{n}.o") for n in HOST_UNITS} if host else {}
     try:
         _compile((obj, src, [f"-DPD_KR={r}", f"-DPD_KPH={ph}", f"-DPD_KW={w}"] + list(defines)), False)
-        if host:
-            _compile((hobj, os.path.join(os.path.dirname(src), "pdenv.hip"), list(defines)), False)
+        for o in hobjs.values():
+            _compile((o, os.path.join(os.path.dirname(src), os.path.basename(o)[:-2] + ".hip"), list(defines)), False)
     finally:
         if tmp:
             shutil.rmtree(tmp, ignore_errors=True)
     out = os.path.join(PKG, f"libpdenv_{name}.so")
-    objs = [obj if os.path.basename(u[0]) == os.path.basename(obj) else
-            (hobj if host and os.path.basename(u[0]) == "pdenv.o" else u[0]) for u in units()]
+    objs = [obj if os.path.basename(u[0]) == os.path.basename(obj) else hobjs.get(os.path.basename(u[0]), u[0])
+            for u in units()]
     subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs, check=True)
     return out

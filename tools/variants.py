@@ -2,7 +2,7 @@
 """Build experiment variants of libpdenv (c3 step-kernel object only) in parallel:
 python tools/variants.py name=-DFOO,-DBAR name2=patch:tools/experiments/no_gust.patch ...
 (patch:<file> compiles a patched copy of csrc/; the product sources are never modified; the item
-"host" also compiles the host unit from it, e.g.
+"host" also compiles the host units from it, e.g.
 idx2=patch:tools/experiments/two_level_index.patch,-DPD_IDX2=1,host; the item unit:R.P.W builds that
 step-kernel object instead of the c3 one -- precision 0/1, phase family 0/1/2, wind 0/1 -- e.g.
 pnt=patch:tools/experiments/policy_nt.patch,unit:0.1.0 for the f64 landing_burn windless (c4) unit)"""
