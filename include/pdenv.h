@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PD_ABI_VERSION 11  /* 4: pd_config.integrator (was padding); 5: pd_count_work, pd_step_sac; 6: cell pieces (pd_cell_piece_info, stats word 44); 7: pd_step_sac_ring, pd_sac_actor, stats word 45; 8: pd_step_sac_fused, pd_atm_table; 9: pd_config.table_flags, pd_tuning, caller scratch for pd_pso_swarm_minima, state/action dims of pd_step_sac_fused; 10: step launches insert their own solved misses (pd_flush_misses optional), explicit list settings turn the auto refill off; 11: pd_pso_step_chunked, pd_rollout_policy_chunked; pd_rollout_sac added later as an additive export (the version stays 11: no layout or existing call changes) */
+#define PD_ABI_VERSION 11  /* 4: pd_config.integrator (was padding); 5: pd_count_work, pd_step_sac; 6: cell pieces (pd_cell_piece_info, stats word 44); 7: pd_step_sac_ring, pd_sac_actor, stats word 45; 8: pd_step_sac_fused, pd_atm_table; 9: pd_config.table_flags, pd_tuning, caller scratch for pd_pso_swarm_minima, state/action dims of pd_step_sac_fused; 10: step launches insert their own solved misses (pd_flush_misses optional), explicit list settings turn the auto refill off; 11: pd_pso_step_chunked, pd_rollout_policy_chunked; pd_rollout_sac, then pd_atm_table_lds, pd_wind_slopes and PD_TABLES_NO_ATM_LDS added later as additive exports (the version stays 11: no layout or existing call changes) */
 #define PD_MAX_PTS 256      /* aero scatter points per table */
 #define PD_MAX_COLS 5       /* AoA columns per aero table */
 #define PD_MAX_TAB 64       /* grid-fin table length */
@@ -81,7 +81,8 @@ typedef enum {
     PD_TABLES_NO_FINE_INDEX = 2,    /* cell pieces reached through the cell / sub-cell records only */
     PD_TABLES_EXACT_ATMOSPHERE = 4, /* the ISA closed form on the device, never the tabulated pieces */
     PD_TABLES_VERBOSE = 8,          /* print the table builders' statistics to stderr at create */
-    PD_TABLES_NO_CARRY = 16         /* the step kernel's searches take no carried interval as a guess */
+    PD_TABLES_NO_CARRY = 16,        /* the step kernel's searches take no carried interval as a guess */
+    PD_TABLES_NO_ATM_LDS = 32       /* no coarse atmosphere table in the 512-thread step kernels' LDS: the closed form */
 } pd_table_flags;
 
 /* One neighbourhood-aero table: scatter points grouped by AoA column, Mach-sorted inside. */
@@ -516,6 +517,16 @@ pd_status pd_cell_piece_info(const pd_params* params, int32_t table, int64_t pie
  * against the long double closed form. */
 pd_status pd_atm_table(const pd_params* params, int32_t precision, const double* alt, int64_t n_alt,
                        double* atm_out, double* max_rel);
+/* The coarse atmosphere table held in LDS by the 512-thread step kernels (binary64 wind handles,
+ * pure throttle, two lanes per env), built and evaluated on the host in the device's order (test
+ * hook; no device needed), as pd_atm_table; n_cells (may be NULL): its cells.  PD_ERR_UNSUPPORTED if
+ * the builder's check is past 1e-14, where a handle would take the closed form. */
+pd_status pd_atm_table_lds(const pd_params* params, const double* alt, int64_t n_alt, double* atm_out,
+                           double* max_rel, int32_t* n_cells);
+/* The wind profiles' interval slopes as those kernels' LDS image tabulates them (binary64): slope of
+ * interval j of profile w at out[w][j], [PD_N_WIND_PROFILES][PD_MAX_WIND]; 0 past a profile's last
+ * interval (test hook; no device needed). */
+pd_status pd_wind_slopes(const pd_params* params, double* out);
 /* Observation / action widths of the handle. */
 int pd_obs_dim(const pd_env* env);
 int pd_action_dim(const pd_env* env);

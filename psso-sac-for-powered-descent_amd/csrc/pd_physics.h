@@ -82,6 +82,13 @@ constexpr int kTayStride = kTayDeg + 1 + 3 * kTayExact + 1;
 // layer's piece)
 constexpr int kAtmDeg = 5, kAtmRec = 2 + 3 * (kAtmDeg + 1), kAtmStride = 2 * kAtmRec;
 constexpr double kAtmW = 100.0;
+// The coarse atmosphere table of the 512-thread step kernels, held in LDS (pd_tables.hip
+// build_atm_lds_table; atmosphere_lds below): cells of kAtlW m, degree kAtlDeg.  A record: centre,
+// the base H of a layer boundary inside the cell or 1e30, the coefficients of p, rho, a, and in its
+// last word the index of the record holding the upper layer's piece (records past the cells')
+constexpr int kAtlDeg = 8, kAtlRec = 2 + 3 * (kAtlDeg + 1) + 1, kAtlStride = kAtlRec, kAtlMaxCells = 96;
+constexpr double kAtlW = 1000.0;
+static_assert(kAtlStride % 2 == 0, "coarse atmosphere records: 16-byte aligned");
 
 // Address spaces of the step kernel's memory: the per-handle parameter block is read through a
 // constant-address-space view (uniform fields become scalar loads into SGPRs), the tables behind
@@ -187,6 +194,10 @@ template <typename R> struct DevParams {
     const R* atm_tab;
     R atm_inv_w;
     int atm_n;
+    // the coarse table in the 512-thread step kernels' LDS image (atmosphere_lds; atl_n records of
+    // cells, 0: none -- the exact formulas); appended, so that every earlier field keeps its offset
+    int atl_n;
+    R atl_inv_w;
 };
 template <typename R> using DP = const PD_AS4 DevParams<R>;
 template <typename T> __device__ __forceinline__ const PD_AS1 T* gbl(const T* p) { return (const PD_AS1 T*)(uint64_t)p; }
@@ -330,6 +341,44 @@ __device__ __forceinline__ void atmosphere(DP<R>& P, const R* isa, R y, R& rho, 
         p = pp;
         rho = pp / (P.isa_R * T);
         a = sqrt(P.isa_kappaR * T);
+    } else {
+        rho = R(0); p = R(0); a = R(0);
+    }
+}
+
+// The 512-thread step kernels' atmosphere: the coarse table in the workgroup's LDS (atl, staged
+// with the static tables; build_atm_lds_table: every piece within 1e-14 of the long double ISA, as
+// the fine table is accepted) -- the cell index, one record, the exact path's own layer test in a
+// cell that holds a boundary, three interleaved Horner chains.  No literal constants, no division
+// outside the boundary cells, an LDS read (not an L2 one) at its head.  No table uploaded
+// (PD_TABLES_NO_ATM_LDS, or a table the builder rejected): the exact path.
+template <typename R>
+__device__ __forceinline__ void atmosphere_lds(DP<R>& P, const R* isa, const R* atl, R y, R& rho, R& p, R& a) {
+    if (P.atl_n == 0) { atmosphere<R, false>(P, isa, y, rho, p, a); return; }
+    R alt = y < R(0) ? R(0) : y;
+    if (alt < P.isa_alt_max) {
+        int k = (int)(alt * P.atl_inv_w);
+        k = k > P.atl_n - 1 ? P.atl_n - 1 : k;
+        const R* rec = atl + k * kAtlStride;
+        R c[kAtlRec];
+#pragma unroll
+        for (int u = 0; u < kAtlRec; ++u) c[u] = rec[u];
+        // a layer boundary inside this cell (c[1] its base H): the exact path's layer test, so that
+        // both take the same side of the pb jump
+        if (c[1] < R(1e29) && P.isa_r * alt / (P.isa_r + alt) >= c[1]) {
+            rec = atl + (int)c[kAtlRec - 1] * kAtlStride;
+#pragma unroll
+            for (int u = 0; u < kAtlRec; ++u) c[u] = rec[u];
+        }
+        const R t = alt - c[0];
+        R fp = c[2 + kAtlDeg], fr = c[2 + 2 * kAtlDeg + 1], fa = c[2 + 3 * kAtlDeg + 2];
+#pragma unroll
+        for (int j = kAtlDeg - 1; j >= 0; --j) {
+            fp = fma(fp, t, c[2 + j]);
+            fr = fma(fr, t, c[2 + kAtlDeg + 1 + j]);
+            fa = fma(fa, t, c[2 + 2 * (kAtlDeg + 1) + j]);
+        }
+        p = fp; rho = fr; a = fa;
     } else {
         rho = R(0); p = R(0); a = R(0);
     }
@@ -546,10 +595,29 @@ __device__ __forceinline__ R np_interp(const R* x, const R* y, int n, R v, const
 // np_interp (no tabulated slopes) with the carried knot j (0..n-2; kCarryWindMask: none) as a
 // guess: x[j] <= v < x[j+1] with j < n - 1 is the in-range search's answer (and implies that neither
 // early-out applies), so a guess that passes reads neither x[0] nor x[n-1]
-template <typename R>
-__device__ __forceinline__ R np_interp_carry(const R* x, const R* y, int n, R v, uint32_t& g, int& res) {
+// SL: the interval's slope (y[j + 1] - y[j]) / (x[j + 1] - x[j]) read from slope[j], tabulated by
+// that division on the same operands (pd_step.h wind_slope: the same bits), in both paths
+template <typename R, bool SL = false>
+__device__ __forceinline__ R np_interp_carry(const R* x, const R* y, int n, R v, uint32_t& g, int& res,
+                                             const R* slope = nullptr) {
     bool ok = g != kCarryWindMask && (int)g < n - 1;
     int j = ok ? (int)g : 0;
+    if constexpr (SL) {
+        R x0 = x[j], x1 = x[j + 1], y0 = y[j], sl = slope[j];
+        ok = ok && x0 <= v && v < x1;
+        res = ok ? kCarryHit : kCarrySearch;
+        if (!ok) {
+            res = kCarrySkip;
+            if (v < x[0]) return y[0];
+            if (v >= x[n - 1]) return y[n - 1];
+            res = kCarrySearch;
+            j = np_interp_search<R>(x, n, v);
+            x0 = x[j]; y0 = y[j]; sl = slope[j];
+            g = (uint32_t)j;
+        }
+        if (x0 == v) return y0;
+        return sl * (v - x0) + y0;
+    }
     R x0 = x[j], x1 = x[j + 1], y0 = y[j], y1 = y[j + 1];   // (rows of 16 knots: j + 1 <= 15)
     ok = ok && x0 <= v && v < x1;
     res = ok ? kCarryHit : kCarrySearch;

@@ -19,6 +19,28 @@ namespace pd {
 
 constexpr int kBlock = 256;
 constexpr int kStepBlock = 256;
+// The step kernel's workgroup size is a function of the instantiation: 512 threads -- one
+// workgroup per CU, so that the static tables are staged once per CU, not twice, and the freed LDS
+// holds the coarse atmosphere table and the wind slopes (StepStatic BIG) -- for the binary64,
+// pure-throttle, wind, two-lanes-per-env, plain-action kernels (c3, c3-descent and their counting
+// instantiation); kStepBlock everywhere else.  Experiment builds: -DPD_WG512=0 (256 everywhere,
+// and neither of the other two), -DPD_ATM_LDS=0 (the exact atmosphere), -DPD_WIND_SLOPE=0
+// (np_interp's own division).
+#ifndef PD_WG512
+#define PD_WG512 1
+#endif
+#ifndef PD_ATM_LDS
+#define PD_ATM_LDS 1
+#endif
+#ifndef PD_WIND_SLOPE
+#define PD_WIND_SLOPE 1
+#endif
+template <typename R, int PHASE, bool WIND, int LPE, int POL, bool RK4, bool SAC> constexpr bool step_big() {
+    return PD_WG512 != 0 && sizeof(R) == 8 && PHASE == 0 && WIND && LPE == 2 && POL == 0 && !RK4 && !SAC;
+}
+template <typename R, int PHASE, bool WIND, int LPE, int POL, bool RK4, bool SAC> constexpr int step_block() {
+    return step_big<R, PHASE, WIND, LPE, POL, RK4, SAC>() ? 512 : kStepBlock;
+}
 constexpr int kScratch = kSys * kSys + kSys + 3 * kNbr + kPay;   // doubles per solve slot
 constexpr int kPendingCap = 4096;     // device-solved neighbourhoods queued per launch
 constexpr int kSolveSlots = 1024;     // global-memory LU scratch slots (one per workgroup, modulo)
@@ -133,7 +155,11 @@ template <typename R> struct LineLds {
 // The tables every step workgroup stages into LDS, in the layout of its LDS (StepLds derives from
 // it): the handle keeps an image of it in HBM (pd_create, fill_step_static) and the kernel
 // prologue copies it with 16-byte loads.
-template <typename R, bool WIND> struct alignas(16) StepStatic {
+// BIG (the 512-thread kernels, step_big): the same layout followed by the wind profiles' interval
+// slopes and the coarse atmosphere table (pd_physics.h kAtl*).  The handle's image of a binary64
+// wind handle is the BIG one; the other kernels copy its leading StepStatic<R, WIND>.
+template <typename R, bool WIND, bool BIG = false> struct StepStatic;
+template <typename R, bool WIND> struct alignas(16) StepStatic<R, WIND, false> {
     // table points as (Mach_p, Mach_p+1) entries, C_D's 256 then C_L's: one 16-byte LDS read per
     // payload pair slot (smach[2p] is point p's Mach for the neighbourhood search)
     alignas(16) R tab[1024];
@@ -145,11 +171,15 @@ template <typename R, bool WIND> struct alignas(16) StepStatic {
     R wsp[WIND ? 800 : 1];
     LineLds<R> lines;
 };
+template <typename R, bool WIND> struct alignas(16) StepStatic<R, WIND, true> : StepStatic<R, WIND, false> {
+    R wsl[800];                   // wind profiles: the slope of a profile's interval j at its knot j
+    alignas(16) R atl[kAtlMaxCells * kAtlStride];   // the coarse atmosphere table (DevParams::atl_n cells)
+};
 
 // The image's contents from the handle's parameter block (host): what the kernel prologue staged
 // field by field before round 5, the same values; the grid-fin interval slopes are the division
 // grid_fin_ca / np_interp would do, on the same operands (IEEE on host and device: same bits)
-template <typename R, bool WIND> void fill_step_static(const DevParams<R>& P, StepStatic<R, WIND>& L) {
+template <typename R, bool WIND> void fill_step_static(const DevParams<R>& P, StepStatic<R, WIND, false>& L) {
     std::memset(&L, 0, sizeof(L));
     for (int t = 0; t < 256; ++t) {
         L.tab[2 * t] = P.cd_mach[t]; L.tab[2 * t + 1] = t < 255 ? P.cd_mach[t + 1] : R(0);
@@ -176,6 +206,20 @@ template <typename R, bool WIND> void fill_step_static(const DevParams<R>& P, St
     }
     for (int k = 0; k < 4; ++k) { L.lines.a[k] = P.line_a[k]; L.lines.nbp[k] = P.line_nbp[k]; L.lines.tay_off[k] = P.tay_off[k]; }
     for (int t = 0; t < 4 * kLineBuckets; ++t) (&L.lines.lb[0][0])[t] = (&P.line_lb[0][0])[t];
+}
+// The slope of interval j of wind profile p: the division np_interp does, on the same operands (IEEE
+// on host and device: same bits); a knot past the profile's last interval is never read
+template <typename R> R wind_slope(const DevParams<R>& P, int p, int j) {
+    if (j + 1 >= P.wind_n[p] || j + 1 >= 16) return R(0);
+    return (P.wind_speed[p][j + 1] - P.wind_speed[p][j]) / (P.wind_alt_km[p][j + 1] - P.wind_alt_km[p][j]);
+}
+// The BIG image; atl: the n_atl words of the coarse atmosphere table's records (P.atl_n cells and
+// the boundary cells' upper pieces; with P.atl_n 0 none is read)
+template <typename R, bool WIND>
+void fill_step_static_big(const DevParams<R>& P, const R* atl, size_t n_atl, StepStatic<R, WIND, true>& L) {
+    fill_step_static<R, WIND>(P, L);
+    for (int t = 0; t < 800; ++t) L.wsl[t] = wind_slope<R>(P, t / 16, t % 16);
+    for (int t = 0; t < kAtlMaxCells * kAtlStride; ++t) L.atl[t] = (size_t)t < n_atl ? atl[t] : R(0);
 }
 
 // ---------------------------------------------------------------- per-env device buffers

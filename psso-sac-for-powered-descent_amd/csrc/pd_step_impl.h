@@ -355,6 +355,8 @@ __device__ __forceinline__ R rbf_miss_wave(const AT& a, DP<R>& P, int table, con
                                            int part, int nparts, bool need) {
     R val = R(0);
     unsigned long long mm = __ballot(need);
+    // (any workgroup size: the slot is the workgroup's modulo kSolveSlots and its lock serialises
+    // the waves that share it, eight of a 512-thread workgroup as four of a 256-thread one)
     const unsigned slot = blockIdx.x % kSolveSlots;
     PD_AS1 double* work = gblw(a.pend.solve_ws) + (size_t)slot * kScratch;
     while (mm) {
@@ -1025,11 +1027,13 @@ __device__ __forceinline__ void actor_forward(const float* __restrict__ W, int64
 // ---------------------------------------------------------------- LDS of one step workgroup
 // (the tables every workgroup stages come first: StepStatic, pd_step.h, copied from the handle's
 // image of it)
-template <typename R, bool WIND, int EPB, bool BAL = false, bool CNT = false> struct StepLds : StepStatic<R, WIND> {
+// KB: the workgroup's threads (pd_step.h step_block); BIG: the 512-thread kernels' image
+template <typename R, bool WIND, int EPB, bool BAL = false, bool CNT = false, int KB = kStepBlock, bool BIG = false>
+struct StepLds : StepStatic<R, WIND, BIG> {
     R gwin[10][EPB];              // the g-load ring of each env of the workgroup (register-resident launches)
-    uint32_t work[kStepBlock / 64][CNT ? kNWork : 1];   // per-wave workload counts (the counting instantiation)
-    double wnx[WIND ? 2 : 1][WIND ? kStepBlock : 1];   // each lane's gust normals of the next (odd) sub-step
-    BalLds<R> bal[BAL ? kStepBlock / 64 : 1];   // LPE 2: balanced-sum space per wave
+    uint32_t work[KB / 64][CNT ? kNWork : 1];   // per-wave workload counts (the counting instantiation)
+    double wnx[WIND ? 2 : 1][WIND ? KB : 1];   // each lane's gust normals of the next (odd) sub-step
+    BalLds<R> bal[BAL ? KB / 64 : 1];   // LPE 2: balanced-sum space per wave
     TabView<R> tdesc[2];          // each table's view, staged once: a lane's table is per lane
 };
 
@@ -1088,13 +1092,19 @@ __device__ __forceinline__ TabView<R> tab_view(DP<R>& P, const R* tab, int table
 template <typename R, int PHASE, int RTD, bool WIND, int LPE, int POL = 0, bool RK4 = false, bool CNT = false,
           bool SAC = false, bool ROLL = false>
 // waves_per_eu(2): caps VGPR+AGPR at 256 so the f64 kernel keeps two waves per SIMD
-__global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
+// (512 threads: four waves per SIMD of one workgroup would need <= 128 registers; two per SIMD of
+// one 512-thread workgroup is the same occupancy as two 256-thread workgroups per CU)
+__global__ __launch_bounds__((step_block<R, PHASE, WIND, LPE, POL, RK4, SAC>()))
+__attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
     SA<R>& a = kargs<R>();
     static_assert(sizeof(a_) > 0);
     static_assert(!ROLL || (SAC && LPE == 16 && !POL && !RK4 && !CNT && RTD == 0 && PHASE <= 1),
                   "ROLL: the SAC kernel of the RL landing burns at 16 lanes per env");
+    // the workgroup's threads (pd_step.h step_block: 512 for c3's kernels, with the BIG image)
+    constexpr int kStepBlock = step_block<R, PHASE, WIND, LPE, POL, RK4, SAC>();
+    constexpr bool kBig = step_big<R, PHASE, WIND, LPE, POL, RK4, SAC>();
     constexpr int EPB = kStepBlock / LPE;   // envs per workgroup
-    __shared__ StepLds<R, WIND, EPB, LPE == 2, CNT> L;
+    __shared__ StepLds<R, WIND, EPB, LPE == 2, CNT, kStepBlock, kBig> L;
 #ifdef PD_STAMP
     unsigned long long acc_[17] = {};   // [7], [8]: rbf2 lookup, evaluation; [9..12] lookup parts; [13..16] post-aero parts
 #endif
@@ -1203,7 +1213,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
     // fill_step_static: the same values, the grid-fin slopes by the same division), every load of
     // a thread issued here -- ahead of the SAC actor's prologue, whose first waits then cover
     // their latency -- and stored after it; then the eval_log cells
-    constexpr int kImg = (int)(sizeof(StepStatic<R, WIND>) / 16);
+    constexpr int kImg = (int)(sizeof(StepStatic<R, WIND, kBig>) / 16);
     constexpr int kLog = (int)(sizeof(LogTableD) / 16);
     constexpr int kPer = (kImg + kLog + kStepBlock - 1) / kStepBlock;
     using V4 = __attribute__((ext_vector_type(4))) unsigned int;
@@ -1247,7 +1257,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
 #pragma unroll
         for (int k = 0; k < kPer; ++k) {
             const int t = threadIdx.x + k * kStepBlock;
-            if (t < kImg) ((V4*)static_cast<StepStatic<R, WIND>*>(&L))[t] = stg[k];
+            if (t < kImg) ((V4*)static_cast<StepStatic<R, WIND, kBig>*>(&L))[t] = stg[k];
             else if (t < kImg + kLog) ((V4*)s_logtab)[t - kImg] = stg[k];
         }
         if constexpr (CNT) { if (threadIdx.x < (kStepBlock / 64) * kNWork) (&L.work[0][0])[threadIdx.x] = 0u; }
@@ -1291,6 +1301,10 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
     // the tabulated atmosphere where it pays: binary32 handles and the windless kernels (c2, c4,
     // c5); the binary64 wind kernels (c3) keep the exact path (pd_physics.h atmosphere)
     constexpr bool kAtmTab = sizeof(R) == 4 || !WIND;
+    // the 512-thread kernels (c3 binary64): the coarse table of their LDS image (pd_physics.h
+    // atmosphere_lds), and the wind profiles' tabulated slopes
+    constexpr bool kAtmLds = kBig && PD_ATM_LDS != 0;
+    constexpr bool kWindSlope = kBig && PD_WIND_SLOPE != 0;
     // (LPE 16 measured 6 % slower with them: its split payload sum is as short as a piece)
     constexpr bool kPcs = !WIND && !RK4 && LPE <= 8 && (PHASE == 0 || (PHASE == 1 && !SAC));
     const R dt = RK4 ? R(0.01) : (PHASE == 0 ? R(0.025) : (PHASE == 1 ? R(0.1) : (R)a.dt_aux));
@@ -1584,7 +1598,8 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
         RS speed;
         if (RK4 ? (sub == 0 && k_have) : k_have) { rho = k_rho; patm = k_patm; asnd = k_asnd; speed = k_speed; }
         else {
-            atmosphere<R, kAtmTab>(P, L.isa, (R)y, rho, patm, asnd);
+            if constexpr (kAtmLds) atmosphere_lds<R>(P, L.isa, L.atl, (R)y, rho, patm, asnd);
+            else atmosphere<R, kAtmTab>(P, L.isa, (R)y, rho, patm, asnd);
             speed = sqrt(vx * vx + vy * vy);
         }
         const R spR = (R)speed;
@@ -1606,7 +1621,8 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
                 if constexpr (kCarry && (PD_CARRY & 1)) {
                     uint32_t wj = carry_get(carry, kCarryWindShift, kCarryWindMask);
                     int wres;
-                    ug = np_interp_carry<R>(walt, wsp, wn, km, wj, wres);
+                    if constexpr (kWindSlope) ug = np_interp_carry<R, true>(walt, wsp, wn, km, wj, wres, L.wsl + e.prof * 16);
+                    else ug = np_interp_carry<R>(walt, wsp, wn, km, wj, wres);
                     carry = carry_set(carry, kCarryWindShift, kCarryWindMask, wj);
                     wc.add_carry(kStCWindHit - kStWork, live && wres == kCarryHit, live && wres == kCarrySearch);
                 } else {
@@ -1984,7 +2000,8 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
         } else {
         vx += (RS)vxd * dts; vy += (RS)vyd * dts; x += vx * dts; y += vy * dts;
         thd += (RS)thdd * dts; th += thd * dts;
-        atmosphere<R, kAtmTab>(P, L.isa, (R)y, k_rho, k_patm, k_asnd);
+        if constexpr (kAtmLds) atmosphere_lds<R>(P, L.isa, L.atl, (R)y, k_rho, k_patm, k_asnd);
+        else atmosphere<R, kAtmTab>(P, L.isa, (R)y, k_rho, k_patm, k_asnd);
         k_speed = sqrt(vx * vx + vy * vy);
         k_have = true;
         ga = pd_atan2<RS>(vy, vx);
@@ -2367,6 +2384,7 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
         // past their table reads; the other workgroups' queued entries were released by their
         // writers (rbf_miss_wave), the acquire below makes them visible here.  (Policy launches
         // have waves that leave early, so no workgroup barrier here: they keep k_insert.)
+        // (the ticket counts workgroups, gridDim.x of them whatever their size)
         __syncthreads();
         if (threadIdx.x == 0) {
             const unsigned int t = atomicAdd(a.pend.ticket, 1u);
@@ -2401,13 +2419,17 @@ __global__ __launch_bounds__(kStepBlock) __attribute__((amdgpu_waves_per_eu(2)))
 
 // ---------------------------------------------------------------- launchers
 template <typename R, int PH, int RT, bool W, int LPE, bool RK> void launch_step(const StepArgs<R>& a, hipStream_t s) {
-    unsigned grid = (unsigned)((a.n * LPE + kStepBlock - 1) / kStepBlock);
+    // the plain and the counting kernel share their workgroup size (pd_step.h step_block); the SAC
+    // kernels keep kStepBlock
+    constexpr int kPlain = step_block<R, PH, W, LPE, 0, RK, false>();
+    const unsigned grid = (unsigned)((a.n * LPE + kStepBlock - 1) / kStepBlock);
+    const unsigned grid_plain = (unsigned)((a.n * LPE + kPlain - 1) / kPlain);
     // the SAC instantiation: heads from the caller (sac_mean) or from the kernel's own actor
     // prologue (sac_mlp.H, pd_step_sac_fused: sac_mean is then NULL and a.actions too)
     const bool sac = a.sac_mean != nullptr || a.sac_mlp.H != 0;
     if constexpr (LPE == 2 && !RK) {
         if ((a.count_work & kArgCount) && !sac) {
-            hipLaunchKernelGGL((k_step<R, PH, RT, W, LPE, 0, RK, true>), dim3(grid), dim3(kStepBlock), 0, s, a);
+            hipLaunchKernelGGL((k_step<R, PH, RT, W, LPE, 0, RK, true>), dim3(grid_plain), dim3(kPlain), 0, s, a);
             return;
         }
     }
@@ -2418,7 +2440,7 @@ template <typename R, int PH, int RT, bool W, int LPE, bool RK> void launch_step
         }
     }
     if (sac) return;   // (no SAC instantiation for this kernel family: pdenv.hip refuses such handles first)
-    hipLaunchKernelGGL((k_step<R, PH, RT, W, LPE, 0, RK>), dim3(grid), dim3(kStepBlock), 0, s, a);
+    hipLaunchKernelGGL((k_step<R, PH, RT, W, LPE, 0, RK>), dim3(grid_plain), dim3(kPlain), 0, s, a);
 }
 
 template <typename R, int PH, bool W, int LPE> void launch_policy_lpe(const StepArgs<R>& a, int64_t n_launch,

@@ -60,6 +60,9 @@ template <typename R> struct HostTables {
     Table<R> cd, cl;                // hash tables of solved neighbourhoods (C_D, C_L)
     std::vector<R> tay;             // Taylor pieces of the clamped query lines (D.tay_off)
     std::vector<R> atm;             // atmosphere cells, D.atm_n of them (empty: the exact formulas)
+    // the coarse atmosphere records of the 512-thread kernels' LDS image (D.atl_n cells, then the
+    // boundary cells' upper pieces; empty: none), part of the uploaded StepStatic image
+    std::vector<R> atl;
     struct Grid {                   // interior candidate grid of one table
         std::vector<unsigned long long> key, sub_key;
         std::vector<int> slot, sub_slot;
@@ -80,6 +83,9 @@ const CellPieces& cell_pieces(const pd_aero_table& t, double a0, double a1, int 
 void ensure_f32(CellPieces& cp);
 // (instantiated for double and float)
 template <typename R> void build_atm_table(const pd_params* P, std::vector<R>& out, int& n_cells, double& max_rel);
+// (instantiated for double: the coarse table exists for binary64 handles)
+template <typename R>
+void build_atm_lds_table(const pd_params* P, std::vector<R>& out, int& n_cells, int& n_rec, double& max_rel);
 
 // The device's Horner evaluation of coefficients q[0..deg] (in R) at t, in R
 template <typename R> R horner_host(const R* q, int deg, R t) {

@@ -1037,6 +1037,67 @@ void build_atm_table(const pd_params* P, std::vector<R>& out, int& n_cells, doub
     }
 }
 
+// The coarse table of the 512-thread step kernels' LDS (pd_physics.h kAtl*, atmosphere_lds): the
+// same method over cells of kAtlW metres at degree kAtlDeg.  Records [0, n_cells): the cells'
+// pieces (of a cell holding a layer boundary the lower layer's, word 1 the boundary's Hb); then one
+// record per boundary cell with its upper layer's piece, its index in the cell record's last word.
+// out holds n_rec records; more than kAtlMaxCells of them (no such ISA): max_rel = infinity.
+template <typename R>
+void build_atm_lds_table(const pd_params* P, std::vector<R>& out, int& n_cells, int& n_rec, double& max_rel) {
+    const double w = kAtlW, top = P->isa_alt_max;
+    n_cells = (int)std::ceil(top / w);
+    n_rec = n_cells;
+    out.assign((size_t)n_cells * kAtlStride, R(0));
+    max_rel = 0;
+    const long double r = P->isa_r;
+    auto layer_of = [&](long double y) {
+        const long double H = r * y / (r + y);
+        int i = 0;
+        for (int k = 0; k < 9; ++k) if ((long double)P->isa_Hb[k] <= H) i = k;
+        return i;
+    };
+    for (int k = 0; k < n_cells; ++k) {
+        const long double lo = (long double)k * w, hi = std::min<long double>((long double)(k + 1) * w, top);
+        const int il = layer_of(lo), ih = layer_of(hi - 1e-9L);
+        // (a cell spans one boundary at most: the ISA's layers are kilometres apart)
+        if (ih > il + 1) { max_rel = INFINITY; return; }
+        long double split = hi;
+        if (ih != il) {   // the boundary y of H = Hb[ih]: y = r Hb / (r - Hb)
+            const long double Hb = P->isa_Hb[ih];
+            split = r * Hb / (r - Hb);
+        }
+        for (int half = 0; half < (ih != il ? 2 : 1); ++half) {
+            const long double a0 = half ? split : lo, a1 = half ? hi : split;
+            const int li = half ? ih : il;
+            if (half) { out.resize((size_t)(n_rec + 1) * kAtlStride, R(0)); }
+            R* rec = out.data() + (size_t)(half ? n_rec : k) * kAtlStride;
+            long double q[3][kAtlDeg + 1];
+            for (int fn = 0; fn < 3; ++fn)
+                fit_poly_ld([&](long double y) { const AtmLd v = atm_exact_ld(P, li, y);
+                                                 return fn == 0 ? v.p : (fn == 1 ? v.rho : v.a); },
+                            a0, a1, kAtlDeg, q[fn]);
+            rec[0] = (R)((a0 + a1) / 2);
+            // (the split as the layer's base H and the exact path's own test, as build_atm_table)
+            rec[1] = half || ih == il ? (R)1e30 : (R)P->isa_Hb[ih];
+            for (int fn = 0; fn < 3; ++fn)
+                for (int j = 0; j <= kAtlDeg; ++j) rec[2 + fn * (kAtlDeg + 1) + j] = (R)q[fn][j];
+            rec[kAtlRec - 1] = R(0);
+            if (half) { out[(size_t)k * kAtlStride + kAtlRec - 1] = (R)n_rec; ++n_rec; }
+            for (int m = 0; m <= 32; ++m) {
+                const long double y = a0 + (a1 - a0) * (m == 0 ? 1e-6L : (m == 32 ? 0.999999L : m / 32.0L));
+                const AtmLd v = atm_exact_ld(P, li, y);
+                const R t = (R)y - rec[0];
+                const long double ex[3] = {v.p, v.rho, v.a};
+                for (int fn = 0; fn < 3; ++fn) {
+                    const R f = horner_host<R>(rec + 2 + fn * (kAtlDeg + 1), kAtlDeg, t);
+                    max_rel = std::max(max_rel, (double)(fabsl((long double)f - ex[fn]) / fabsl(ex[fn])));
+                }
+            }
+        }
+    }
+    if (n_rec > kAtlMaxCells) max_rel = INFINITY;
+}
+
 // The interior candidate grid of table tb (0: C_D, 1: C_L): Mach [0, 10] x AoA abscissa [a0, a1]
 // (C_D in [-radians(10), radians(10)], C_L in [0, 10]) in nm x na cells.  800 x 32 / 800 x 400
 // cells, refined cells in 8 x 8 sub-cells, two-region sub-cells split by their bisector: < 0.1 %
@@ -1224,6 +1285,17 @@ template <typename R> pd_status build_host_tables(const pd_params* p, const pd_c
         if (err_atm <= (sizeof(R) == 8 ? 1e-14 : 4e-6)) { D.atm_n = n_atm; D.atm_inv_w = (R)(1.0 / kAtmW); }
         else H.atm.clear();
     }
+    // the coarse table of the 512-thread step kernels' LDS image (binary64 wind handles: c3);
+    // PD_TABLES_NO_ATM_LDS or a table past 1e-14: none, those kernels take the exact formulas
+    D.atl_n = 0; D.atl_inv_w = (R)(1.0 / kAtlW);
+    if constexpr (sizeof(R) == 8) if (c->enable_wind && !(c->table_flags & PD_TABLES_NO_ATM_LDS)) {
+        int n_cells = 0, n_rec = 0;
+        double err_atl = 0;
+        build_atm_lds_table<R>(p, H.atl, n_cells, n_rec, err_atl);
+        if (verbose) fprintf(stderr, "pdenv LDS atmosphere table: %d cells, %d records, max rel err %.3g\n", n_cells, n_rec, err_atl);
+        if (err_atl <= 1e-14) D.atl_n = n_cells;
+        else H.atl.clear();
+    }
     // interior candidate grids: C_D abscissa in [-radians(10), radians(10)], C_L in [0, 10]
     for (int tb = 0; tb < 2; ++tb) grid_geometry(tb, H.grid[tb].nm, H.grid[tb].na, H.grid[tb].a0, H.grid[tb].a1);
     // cell pieces for the interior queries (PD_TABLES_NO_CELL_PIECES: payload sums only): binary64
@@ -1271,5 +1343,6 @@ template pd_status build_host_tables<double>(const pd_params*, const pd_config*,
 template pd_status build_host_tables<float>(const pd_params*, const pd_config*, HostTables<float>&);
 template void build_atm_table<double>(const pd_params*, std::vector<double>&, int&, double&);
 template void build_atm_table<float>(const pd_params*, std::vector<float>&, int&, double&);
+template void build_atm_lds_table<double>(const pd_params*, std::vector<double>&, int&, int&, double&);
 
 }  // namespace pd

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -270,7 +271,7 @@ pd_status validate(const pd_params* p, const pd_config* c) {
     if (c->precision != PD_F64 && c->precision != PD_F32) return fail(PD_ERR_INVALID, "bad precision");
     if (c->integrator != PD_INTEG_REFERENCE && c->integrator != PD_INTEG_RK4) return fail(PD_ERR_INVALID, "bad integrator");
     if (c->table_flags & ~(PD_TABLES_NO_CELL_PIECES | PD_TABLES_NO_FINE_INDEX | PD_TABLES_EXACT_ATMOSPHERE | PD_TABLES_VERBOSE |
-                           PD_TABLES_NO_CARRY))
+                           PD_TABLES_NO_CARRY | PD_TABLES_NO_ATM_LDS))
         return fail(PD_ERR_INVALID, "unknown table_flags bits");
     if (c->integrator == PD_INTEG_RK4 && (c->phase != PD_PHASE_PURE_THROTTLE || c->enable_wind))
         return fail(PD_ERR_UNSUPPORTED, "the RK4 integrator (non-parity, BASELINE c2) exists for "
@@ -353,9 +354,15 @@ template <typename R> pd_status create_impl(const pd_params* p, const pd_config*
         }
     }
     {
-        // the step kernels' LDS tables as one image (pd_step.h StepStatic), copied by their prologue
-        std::vector<uint8_t> h(c->enable_wind ? sizeof(StepStatic<R, true>) : sizeof(StepStatic<R, false>));
-        if (c->enable_wind) fill_step_static<R, true>(D, *(StepStatic<R, true>*)h.data());
+        // the step kernels' LDS tables as one image (pd_step.h StepStatic), copied by their prologue;
+        // binary64 wind handles: the BIG image (the 512-thread kernels', of which the other kernels
+        // copy the leading StepStatic<R, true>)
+        constexpr bool kBigImg = sizeof(R) == 8;
+        std::vector<uint8_t> h(c->enable_wind ? sizeof(StepStatic<R, true, kBigImg>) : sizeof(StepStatic<R, false>));
+        if (c->enable_wind) {
+            if constexpr (kBigImg) fill_step_static_big<R, true>(D, H.atl.data(), H.atl.size(), *(StepStatic<R, true, true>*)h.data());
+            else fill_step_static<R, true>(D, *(StepStatic<R, true>*)h.data());
+        }
         else fill_step_static<R, false>(D, *(StepStatic<R, false>*)h.data());
         if ((st = upload(e, h, &D.stage_img))) return st;
     }
@@ -820,6 +827,44 @@ pd_status pd_atm_table(const pd_params* p, int32_t precision, const double* alt,
                        double* max_rel) {
     if (!p || !max_rel || n_alt < 0 || (n_alt && (!alt || !atm_out))) return fail(PD_ERR_INVALID, "pd_atm_table: bad arguments");
     with_real(precision != PD_F32, [&](auto r) { eval_atm_table<decltype(r)>(p, alt, n_alt, atm_out, max_rel); });
+    return PD_OK;
+}
+// the coarse LDS table (atmosphere_lds, pd_physics.h) on the host, in binary64, in the device's order
+pd_status pd_atm_table_lds(const pd_params* p, const double* alt, int64_t n_alt, double* atm_out, double* max_rel,
+                           int32_t* n_cells_out) {
+    if (!p || !max_rel || n_alt < 0 || (n_alt && (!alt || !atm_out))) return fail(PD_ERR_INVALID, "pd_atm_table_lds: bad arguments");
+    std::vector<double> atl;
+    int n_cells = 0, n_rec = 0;
+    build_atm_lds_table<double>(p, atl, n_cells, n_rec, *max_rel);
+    if (n_cells_out) *n_cells_out = n_cells;
+    if (!(*max_rel <= 1e-14)) return fail(PD_ERR_UNSUPPORTED, "pd_atm_table_lds: the table is past 1e-14 (handles take the exact formulas)");
+    const double inv_w = 1.0 / kAtlW;
+    for (int64_t i = 0; i < n_alt; ++i) {
+        const double y = alt[i], al = y < 0.0 ? 0.0 : y;
+        double out[3] = {0.0, 0.0, 0.0};
+        if (al < p->isa_alt_max) {
+            int k = (int)(al * inv_w);
+            k = k > n_cells - 1 ? n_cells - 1 : k;
+            const double* rec = atl.data() + (size_t)k * kAtlStride;
+            if (rec[1] < 1e29 && p->isa_r * al / (p->isa_r + al) >= rec[1]) rec = atl.data() + (size_t)(int)rec[kAtlRec - 1] * kAtlStride;
+            const double t = al - rec[0];
+            for (int fn = 0; fn < 3; ++fn) out[fn] = horner_host<double>(rec + 2 + fn * (kAtlDeg + 1), kAtlDeg, t);
+        }
+        atm_out[3 * i] = out[1]; atm_out[3 * i + 1] = out[0]; atm_out[3 * i + 2] = out[2];
+    }
+    return PD_OK;
+}
+// the wind profiles' interval slopes as the 512-thread kernels' LDS image tabulates them
+// (pd_step.h wind_slope), binary64: out [PD_N_WIND_PROFILES][PD_MAX_WIND]
+pd_status pd_wind_slopes(const pd_params* p, double* out) {
+    if (!p || !out) return fail(PD_ERR_INVALID, "pd_wind_slopes: bad arguments");
+    static_assert(PD_N_WIND_PROFILES * PD_MAX_WIND == 800, "wind profile tables");
+    auto D = std::make_unique<DevParams<double>>();
+    for (int w = 0; w < PD_N_WIND_PROFILES; ++w) {
+        D->wind_n[w] = p->wind_n[w];
+        for (int j = 0; j < PD_MAX_WIND; ++j) { D->wind_alt_km[w][j] = p->wind_alt_km[w][j]; D->wind_speed[w][j] = p->wind_speed[w][j]; }
+    }
+    for (int t = 0; t < 800; ++t) out[t] = wind_slope<double>(*D, t / PD_MAX_WIND, t % PD_MAX_WIND);
     return PD_OK;
 }
 pd_status pd_cell_piece_info(const pd_params* p, int32_t table, int64_t piece, double* out, int32_t n_out) {

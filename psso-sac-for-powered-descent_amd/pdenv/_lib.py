@@ -83,6 +83,7 @@ class PdConfig(C.Structure):
 
 # pd_table_flags
 TABLES_NO_CELL_PIECES, TABLES_NO_FINE_INDEX, TABLES_EXACT_ATMOSPHERE, TABLES_VERBOSE, TABLES_NO_CARRY = 1, 2, 4, 8, 16
+TABLES_NO_ATM_LDS = 32
 
 
 class PdTuning(C.Structure):
@@ -100,7 +101,7 @@ EXPORTS = ["pd_abi_version", "pd_sizeof_params", "pd_sizeof_config", "pd_last_er
            "pd_action_dim", "pd_step_sac", "pd_pso_swarm_minima", "pd_pso_update_bests", "pd_cell_piece_info",
            "pd_step_sac_ring", "pd_sac_actor", "pd_step_sac_fused", "pd_atm_table", "pd_set_tuning", "pd_get_tuning",
            "pd_pso_swarm_minima_scratch_bytes", "pd_step_n_info", "pd_pso_step_chunked", "pd_rollout_policy_chunked",
-           "pd_rollout_sac"]
+           "pd_rollout_sac", "pd_atm_table_lds", "pd_wind_slopes"]
 ABI_VERSION = 11
 
 _lib = None
@@ -164,6 +165,8 @@ def load(path=None):
     L.pd_count_work.argtypes = [vp, I32]
     L.pd_cell_piece_info.argtypes = [P(PdParams), I32, I64, P(C.c_double), I32]
     L.pd_atm_table.argtypes = [P(PdParams), I32, vp, I64, vp, vp]
+    L.pd_atm_table_lds.argtypes = [P(PdParams), vp, I64, vp, vp, vp]
+    L.pd_wind_slopes.argtypes = [P(PdParams), vp]
     L.pd_atmosphere.argtypes = [vp, vp, vp, I64, vp]
     L.pd_get_gload_window.argtypes = [vp, vp, vp, vp, vp, vp]
     L.pd_get_wind_state.argtypes = [vp, vp, vp, vp, vp]
@@ -183,7 +186,7 @@ def load(path=None):
                  "pd_get_wind_state", "pd_set_wind_state", "pd_get_counters", "pd_set_counters",
                  "pd_checkpoint_save", "pd_checkpoint_load", "pd_atmosphere", "pd_cell_piece_info",
                  "pd_step_sac_ring", "pd_sac_actor", "pd_step_sac_fused", "pd_atm_table", "pd_set_tuning",
-                 "pd_get_tuning"):
+                 "pd_get_tuning", "pd_atm_table_lds", "pd_wind_slopes"):
         getattr(L, name).restype = C.c_int
     L.pd_sizeof_params.restype = C.c_size_t
     L.pd_sizeof_config.restype = C.c_size_t
