@@ -300,7 +300,7 @@ pd_status pd_step_sac_ring(pd_env* env, const float* heads, int32_t deterministi
  * shared_net layers, then mean, then log_std.  hidden 128, 256 or 512 (else PD_ERR_UNSUPPORTED),
  * state_dim <= 16, action_dim <= 8, n_hidden_layers <= 8; every parameter 16-byte aligned (else
  * PD_ERR_UNSUPPORTED).  f32 sums in another order than torch's GEMMs: equal to f32 rounding.  Runs
- * on the current HIP device. */
+ * on the current HIP device.  n = 0: PD_OK without a launch (obs and heads may be NULL then). */
 pd_status pd_sac_actor(int64_t n, int32_t state_dim, int32_t hidden, int32_t n_hidden_layers, int32_t action_dim,
                        const float* obs, const float* const* params, float* heads, void* stream);
 /* The whole SAC collection step (sac_pytorch_powered_descent.py:160-183: actor.sample on the

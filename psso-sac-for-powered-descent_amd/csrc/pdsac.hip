@@ -33,7 +33,7 @@ extern "C" {
 pd_status pd_sac_actor(int64_t n, int32_t state_dim, int32_t hidden, int32_t n_hidden_layers, int32_t action_dim,
                        const float* obs, const float* const* params, float* heads, void* stream) {
     if (n < 0 || state_dim < 1 || state_dim > 16 || n_hidden_layers < 1 || n_hidden_layers > pd::kSacMaxLayers ||
-        action_dim < 1 || action_dim > 8 || !params || !heads || (n > 0 && !obs))
+        action_dim < 1 || action_dim > 8 || !params || (n > 0 && (!obs || !heads)))   // (an empty torch tensor: NULL)
         return pd::set_error(PD_ERR_INVALID, "pd_sac_actor: bad arguments");
     if (hidden != 128 && hidden != 256 && hidden != 512)
         return pd::set_error(PD_ERR_UNSUPPORTED, "pd_sac_actor: hidden width 128, 256 or 512 only");

@@ -64,6 +64,38 @@ def test_argument_checks_before_any_launch():
     assert L.pd_get_tuning(None, C.byref(t)) == _lib.PD_ERR_INVALID
 
 
+def test_sac_actor_refuses_shapes_outside_its_domain():
+    """pd_sac_actor's declared domain -- S 1..16, A 1..8, H in {128, 256, 512}, L 1..8, n >= 0 --
+    is refused at its edges before any launch (the pointers are never dereferenced): PD_ERR_INVALID
+    for a dimension out of range, a negative n or a null layer parameter, PD_ERR_UNSUPPORTED for a
+    hidden width without an instantiation."""
+    import pdenv
+    from pdenv import _lib
+    L = pdenv.load()
+    vp = C.c_void_p
+    ok = vp(0x10000)
+    params = (vp * 20)(*([0x10000] * 20))                     # (enough for 8 layers and the heads)
+
+    def call(n=64, S=2, H=256, nl=2, A=1, obs=ok, params=params, heads=ok):
+        return L.pd_sac_actor(n, S, H, nl, A, obs, params, heads, None)
+
+    for H in (64, 384):
+        assert call(H=H) == _lib.PD_ERR_UNSUPPORTED and b"hidden" in L.pd_last_error()
+    for kw in (dict(S=0), dict(S=17), dict(A=0), dict(A=9), dict(nl=0), dict(nl=9), dict(n=-1)):
+        assert call(**kw) == _lib.PD_ERR_INVALID, kw
+    # a dimension out of range is INVALID whatever the hidden width
+    assert call(S=17, H=64) == _lib.PD_ERR_INVALID
+    for k in (0, 1, 2, 3):                                    # a null weight or bias of either layer
+        bad = (vp * 20)(*([0x10000] * 20))
+        bad[k] = 0
+        assert call(params=bad) == _lib.PD_ERR_INVALID and b"layer" in L.pd_last_error(), k
+    assert call(params=None) == _lib.PD_ERR_INVALID and call(heads=None) == _lib.PD_ERR_INVALID
+    assert call(obs=None) == _lib.PD_ERR_INVALID
+    # n = 0: nothing to do, whatever obs and heads are (an empty torch tensor's pointer is NULL)
+    assert call(n=0, obs=None) == _lib.PD_OK and call(n=0, obs=None, heads=None) == _lib.PD_OK
+    assert call(n=0, S=17) == _lib.PD_ERR_INVALID and call(n=0, H=64) == _lib.PD_ERR_UNSUPPORTED
+
+
 def test_no_gpu_create_fails_loudly():
     """Without a HIP device the product refuses to run (no CPU fallback)."""
     import torch

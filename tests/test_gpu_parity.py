@@ -1017,7 +1017,8 @@ def test_sac_ring_step_draws_rows_priorities(pd):
 
 
 @pytest.mark.parametrize("S,A,H,L,lpe", [(2, 1, 256, 2, 0), (2, 1, 128, 3, 0), (5, 4, 256, 2, 16),
-                                          (2, 1, 256, 2, 2), (2, 1, 512, 2, 0)])
+                                          (2, 1, 256, 2, 2), (2, 1, 512, 2, 0), (5, 4, 128, 3, 16),
+                                          (2, 1, 256, 8, 0)])
 def test_sac_fused_step_equals_two_launches(pd, S, A, H, L, lpe):
     """pd_step_sac_fused (the Actor's MLP in the step kernel's prologue: c5's whole collection step
     in one launch) against pd_sac_actor + pd_step_sac_ring on a twin env: the same heads, eps,

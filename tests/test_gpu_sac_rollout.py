@@ -110,6 +110,7 @@ def per_step_loop(pd, actor, N, T, deterministic, phase, cfg):
     (5, 4, 256, 2, "f64", False, True),
     (2, 1, 256, 2, "f32", False, True),
     (2, 1, 256, 2, "f64", False, False),
+    (5, 4, 128, 1, "f64", False, True),
 ])
 def test_rollout_equals_per_step_loop_bitwise(pd, S, A, H, L, prec, windy, deterministic):
     """pd_rollout_sac against a loop of pd_step_sac_fused calls on a twin handle (same seed and
