@@ -354,6 +354,47 @@ pd_status pd_rollout_sac(pd_env* env, int32_t state_dim, int32_t action_dim, int
                          float log_std_min, float log_std_max, float max_action, int32_t reset_first,
                          int32_t max_steps, void* ret, int32_t* steps, uint8_t* done, int8_t* trunc_id,
                          float* actions_out, void* rewards_out, void* stream);
+/* SAC data collection, n_steps steps of every env per call: the driver's collection loop
+ * (sac_pytorch_powered_descent.py:160-183: select_action, env.step, buffer.add, reset at an
+ * episode's end) for the span between two learner updates, during which the actor is fixed.  The
+ * call is n_steps consecutive pd_step_sac_fused steps -- the actor's forward pass (sac_pytorch.py:
+ * 129-159), Actor.sample (:161-179), the env step, the replay row (:27-35) with its priority
+ * (:76-83) -- with the actor INSIDE the step kernel's fused-step loop, as in pd_rollout_sac: a chain
+ * of launches of at most pd_tuning.step_fuse steps, no host synchronisation, no allocation.  The
+ * results equal a loop of n_steps pd_step_sac_fused calls bit for bit, and do not depend on
+ * step_fuse or on how the steps are split into calls.
+ *  state_dim .. params, deterministic, log_std_min / log_std_max, max_action: as pd_rollout_sac
+ *            (same checks; hidden 128 or 256); eps is drawn as pd_step_sac_ring draws it (Philox
+ *            keyed by env, episode, step)
+ *  Envs auto-reset per pd_config.auto_reset, as in pd_step_sac_fused; none freezes.
+ *  ring, ring_state != NULL (ring mode): the replay buffer's rows [capacity][2S + A + 2]; step t's
+ *            row of env i goes to (ring_state[0] + t N + i) mod capacity with priorities[row] =
+ *            *max_priority (priorities may be NULL); each launch's last workgroup advances
+ *            ring_state[0] (position) and ring_state[1] (size, capped at capacity) by its steps x N;
+ *            ring_state[2] must be 0 between launches.  n_steps x N <= capacity (the workgroups of
+ *            one launch run at different steps: its rows must not alias) and capacity x (2S + A + 2)
+ *            < 2^32, else PD_ERR_INVALID
+ *  ring, ring_state == NULL (slab mode, for ranks that gather): ring is [n_steps][N][2S + A + 2];
+ *            capacity and priorities are ignored; n_steps x N x (2S + A + 2) < 2^32
+ *  obs32   : [N][S] float32, OUTPUT ONLY (may be NULL): the observation the actor sees next, after
+ *            any reset, after the last step.  Unlike pd_step_sac_fused, which reads obs32 as the
+ *            previous step left it, the first step's observation is formed from the handle's
+ *            register state -- the value a preceding step or pd_observe, cast to float32, would have
+ *            left there
+ *  eps_out : [n_steps][N][A] float32; reward: [n_steps][N] handle precision; done, truncated:
+ *            [n_steps][N] uint8; trunc_id: [n_steps][N] int8 -- pd_step_n's per-step outputs (the
+ *            episode ends the in-kernel resets would otherwise hide).  Each may be NULL.
+ *  n_steps == 0: PD_OK, nothing launched or written (the actor and the handle are still checked,
+ *            ring and the outputs are not looked at and may be NULL); n_steps < 0: PD_ERR_INVALID.
+ * Handle requirements: those of pd_rollout_sac.  PD_ERR_UNSUPPORTED, with nothing launched and the
+ * cause in pd_last_error, for a handle that does not step 16 lanes per env and for hidden 512
+ * (callers loop pd_step_sac_fused).  (additive export, ABI 11) */
+pd_status pd_collect_sac(pd_env* env, int32_t state_dim, int32_t action_dim, int32_t hidden,
+                         int32_t n_hidden_layers, const float* const* params, int32_t deterministic,
+                         float log_std_min, float log_std_max, float max_action, int32_t n_steps,
+                         float* ring, int64_t capacity, long long* ring_state, float* priorities,
+                         const float* max_priority, float* obs32, float* eps_out, void* reward,
+                         uint8_t* done, uint8_t* truncated, int8_t* trunc_id, void* stream);
 /* Multi-step rollout with device-resident actions [T][N][A]: the fused launches of pd_step_n
  * (per-step launches for the other phases), rewards accumulated into reward_sum [N] (may be
  * NULL), no per-step outputs.  No host synchronisation. */

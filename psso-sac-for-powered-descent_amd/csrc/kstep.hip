@@ -2,7 +2,8 @@
 // (precision, phase family, wind) triple, chosen by -DPD_KR (0 double, 1 float), -DPD_KPH
 // (0 pure throttle, 1 landing_burn, 2 the other phases) and -DPD_KW (0/1).  pdenv/build.py
 // compiles this file once per triple, in parallel, and links the objects into libpdenv.so.
-// -DPD_KROLL=1 (with PD_KPH 0 or 1): the unit holds the triple's SAC rollout kernel only.
+// -DPD_KROLL=1 (with PD_KPH 0 or 1): the unit holds the triple's SAC rollout kernel only;
+// -DPD_KROLL=2: its SAC collection kernel (pd_collect_sac) only.
 #include "pd_step_impl.h"
 
 #if !defined(PD_KR) || !defined(PD_KPH) || !defined(PD_KW)
@@ -27,10 +28,15 @@ constexpr bool KW = PD_KW != 0;
 // RL and PD_RTD_NONE share the RL instantiation; PSO exists for the two landing burns, with the
 // policy-rollout (fused actor) kernels.  -DPD_KLPE=n (experiments): the RL kernel at n lanes only.
 #if defined(PD_KROLL)
-// the SAC rollout kernel (pd_rollout_sac: RL landing burns, 16 lanes per env) and nothing else:
-// units of their own, so that they compile next to the step kernels' units
+// the SAC rollout kernel (pd_rollout_sac: RL landing burns, 16 lanes per env) or the SAC collection
+// kernel (pd_collect_sac, the same handles) and nothing else: units of their own, so that they
+// compile next to the step kernels' units
 static_assert(PD_KPH < 2, "SAC rollout unit: the two landing burns");
+#if PD_KROLL == 2
+template void launch_sac_collect<KR, PD_KPH, KW>(const StepArgs<KR>&, hipStream_t);
+#else
 template void launch_sac_roll<KR, PD_KPH, KW>(const StepArgs<KR>&, hipStream_t);
+#endif
 #elif defined(PD_KRK4)
 // the non-parity RK4 mode (pure throttle, no wind; -DPD_KPH=0 -DPD_KW=0): LPE 2 and 16
 static_assert(PD_KPH == 0 && PD_KW == 0, "RK4 unit: pure throttle without wind");

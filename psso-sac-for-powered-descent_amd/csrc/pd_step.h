@@ -285,6 +285,10 @@ __device__ void insert_pending(unsigned long long* count, const unsigned long lo
 }
 
 constexpr int kArgCount = 1, kArgNoCarry = 2;   // StepArgs::count_work bits
+// k_step's ROLL parameter: the actor inside the fused-step loop (SAC, 16 lanes per env) -- off, whole
+// episodes with freezing envs (pd_rollout_sac), or collection steps with auto-reset and the replay
+// ring (pd_collect_sac)
+constexpr int kRollOff = 0, kRollEpisodes = 1, kRollCollect = 2;
 template <typename R> struct StepArgs {
     uint64_t P;                      // const DevParams<R>* (read through a constant-AS view)
     EnvBufs<R> b;
@@ -367,5 +371,11 @@ template <typename R, int PH, bool W, int LPE> void launch_policy_lpe(const Step
                                                                       hipStream_t s);
 // the SAC rollout kernel (RL landing burns, 16 lanes per env), in translation units of its own
 template <typename R, int PH, bool W> void launch_sac_roll(const StepArgs<R>& a, hipStream_t s);
+// and the SAC collection kernel (pd_collect_sac: k_step<..., SAC, kRollCollect>), likewise.  It reads
+// the fields of pd_step_sac_fused's launch with n_fused steps: step f's row at ring position
+// (ring_state; slab: 0) + f N + i, sac_eps_out / reward / done / trunc / trunc_id as rows f of
+// [n_fused][N] arrays, obs32 written after the last step, the ring advanced by n_fused N at the
+// launch's end (the host offsets the pointers per launch); none of the roll_* fields
+template <typename R, int PH, bool W> void launch_sac_collect(const StepArgs<R>& a, hipStream_t s);
 
 }  // namespace pd

@@ -1089,8 +1089,15 @@ __device__ __forceinline__ TabView<R> tab_view(DP<R>& P, const R* tab, int table
 // as frozen policy-rollout lanes are; the loop ends, workgroup-uniform, when the workgroup has
 // no live env left.  Per env: the return (rewards added in step order, a register), the episode
 // length, the terminal done and trunc_id, and optional action / reward traces.
+// ROLL = kRollCollect: the pd_collect_sac instantiation, the same loop head (the observation rows
+// from the register state, the actor's tile, the heads in LDS) around the per-step SAC kernel's
+// step: every valid env live throughout, auto-reset in registers per config, step f's transition
+// row at ring position (or slab row) + f N + i with its priority, the per-step outputs at row f,
+// obs32 after the last step; the launch's ring ticket advances the ring by n_fused N rows.  The
+// freeze, b.fin, the returns and the traces are compiled away.  The results equal a loop of
+// pd_step_sac_fused launches bit for bit.
 template <typename R, int PHASE, int RTD, bool WIND, int LPE, int POL = 0, bool RK4 = false, bool CNT = false,
-          bool SAC = false, bool ROLL = false>
+          bool SAC = false, int ROLL = kRollOff>
 // waves_per_eu(2): caps VGPR+AGPR at 256 so the f64 kernel keeps two waves per SIMD
 // (512 threads: four waves per SIMD of one workgroup would need <= 128 registers; two per SIMD of
 // one 512-thread workgroup is the same occupancy as two 256-thread workgroups per CU)
@@ -1104,6 +1111,7 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
     constexpr int kStepBlock = step_block<R, PHASE, WIND, LPE, POL, RK4, SAC>();
     constexpr bool kBig = step_big<R, PHASE, WIND, LPE, POL, RK4, SAC>();
     constexpr int EPB = kStepBlock / LPE;   // envs per workgroup
+    constexpr bool kEpi = ROLL == kRollEpisodes, kCol = ROLL == kRollCollect;
     __shared__ StepLds<R, WIND, EPB, LPE == 2, CNT, kStepBlock, kBig> L;
 #ifdef PD_STAMP
     unsigned long long acc_[17] = {};   // [7], [8]: rbf2 lookup, evaluation; [9..12] lookup parts; [13..16] post-aero parts
@@ -1161,7 +1169,7 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
         if (!a.use_list) live = live && ev(a.b.fin, ui) == 0;
     }
     // ROLL: an env that ended in an earlier launch of the rollout stays frozen
-    if constexpr (ROLL) live = live && ev(a.b.fin, ui) == 0;
+    if constexpr (kEpi) live = live && ev(a.b.fin, ui) == 0;
     // role -> (table, part): LPE 1: both tables on one lane; else table = role / (LPE/2)
     constexpr int nparts = LPE >= 2 ? LPE / 2 : 1;
     const int my_table = LPE >= 2 ? role / nparts : 0;   // 0 = C_D, 1 = C_L
@@ -1367,7 +1375,7 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
     // ROLL: the env's return so far (zeroed at the call's start, carried between the launches of
     // the chain in roll_ret) and the store of its results (role-0 lane of a live env)
     R racc = R(0);
-    if constexpr (ROLL) { if (live) racc = ldv(a.roll_ret, ui); }
+    if constexpr (kEpi) { if (live) racc = ldv(a.roll_ret, ui); }
     auto roll_store = [&](int steps, int dn_, int id_, bool fin_) {
         if (role != 0) return;
         uint32_t uo = ui;
@@ -1515,11 +1523,12 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
                 const float sd = expf(ls);
                 const float ek = a.sac_draw ? ed[k] : ldv(a.sac_eps + k, ui * AD);
                 xk = m + sd * ek;
-                if (a.sac_eps_out && role == 0 && live) ev(a.sac_eps_out + k, ui * AD) = ek;
+                // (collect: row f of [n_fused][N][A])
+                if (a.sac_eps_out && role == 0 && live) ev(a.sac_eps_out + (kCol ? fo * AD : (size_t)0) + k, ui * AD) = ek;
             }
             uf[k] = tanhf(xk) * a.sac_max;
             if (a.sac_act && role == 0 && live) ev(a.sac_act + k, ui * AD) = uf[k];
-            if constexpr (ROLL) {   // the action trace: row roll_t0 + f of [T][N][A]
+            if constexpr (kEpi) {   // the action trace: row roll_t0 + f of [T][N][A]
                 if (a.roll_act && role == 0 && live)
                     ev(a.roll_act + (size_t)(a.roll_t0 + f) * (size_t)N * (size_t)AD + k, ui * AD) = uf[k];
             }
@@ -1540,9 +1549,10 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
     // pd_step_sac: the transition row of this step starts with the observation of its start state
     // (row srow: the env's, or in ring mode its row of the replay ring, (position + i) mod capacity)
     constexpr int kObsKind = RTD == 1 ? (PHASE == 0 ? 1 : 2) : (PHASE == 0 ? 0 : (PHASE == 1 ? 3 : -1));
-    uint32_t srow = ui;
+    // (collect: step f's rows follow step f - 1's, n_fused N <= capacity rows per launch: one wrap)
+    uint32_t srow = kCol ? (uint32_t)fo + ui : ui;
     if (SAC && a.ring_state) {
-        const int64_t rp = ring_pos0 + (int64_t)i;
+        const int64_t rp = ring_pos0 + (kCol ? (int64_t)fo : (int64_t)0) + (int64_t)i;
         srow = (uint32_t)(rp >= a.ring_cap ? rp - a.ring_cap : rp);
     }
     if (SAC && a.slab && role == 0 && live) {
@@ -2211,7 +2221,7 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
     PD_ACC(5, t_rtd - t_loop);
     // ---- outputs of step f (role 0 of the env's lane group)
     // (ROLL: an episode's end freezes the env below, whatever cfg.auto_reset says)
-    const bool ended = !POL && !ROLL && a.auto_reset && (dn || tr);
+    const bool ended = !POL && !kEpi && a.auto_reset && (dn || tr);
     wc.add(kStResets - kStWork, ended && role == 0 && live);
     k_have = !ended;
     // (binary32: the next step starts from the rounded state; its speed from the rounded velocity,
@@ -2227,7 +2237,7 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
             obs_write<R>(P2, ok, s, a.obs + fo * obs_dim(ok), uo);
         }
         if (a.reward) ev(a.reward + fo, ui) = rew;
-        if constexpr (ROLL) {
+        if constexpr (kEpi) {
             // evaluate_agent's total_reward += reward (sac_pytorch_powered_descent.py:234-251),
             // in step order in the handle's precision; the reward trace's row roll_t0 + f
             racc += rew;
@@ -2268,12 +2278,14 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
         e.ts = e.ts + 1;
         e.act0 = gdeg_out; e.act1 = dcmdl_out; e.act2 = dcmdr_out;
     }
-    if (SAC && a.obs32 && role == 0 && live) {   // pd_step_sac: what the actor sees next (after any reset)
+    // (collect: the loop head forms every later step's observation from the registers; the last
+    // step's goes to obs32 for whatever call follows)
+    if (SAC && a.obs32 && role == 0 && live && (!kCol || f == nf - 1)) {   // pd_step_sac: what the actor sees next (after any reset)
         const int ok = kObsKind >= 0 ? kObsKind : P2.obs_kind;
         const uint32_t S = (uint32_t)obs_dim(ok);
         obs_eval<R>(P2, ok, e.s, [&](int k, R v) { ev(a.obs32, ui * S + (uint32_t)k) = (float)v; });
     }
-    if constexpr (ROLL) {
+    if constexpr (kEpi) {
         // `done or truncated` ends the episode: the env is stored once, with its terminal
         // (pre-reset) state, its results written and b.fin set for the rollout's later launches;
         // its lanes freeze -- convergent with the wave for the cooperative miss solve, writing
@@ -2360,7 +2372,7 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
     PD_T(t_store);
     // (ROLL: an env still live has run all nf steps of the launch -- the loop leaves early only
     // with no live env -- and goes on in the rollout's next launch, or the caller's next call)
-    if constexpr (ROLL) { if (live) roll_store(a.roll_t0 + nf, 0, e.tid, false); }
+    if constexpr (kEpi) { if (live) roll_store(a.roll_t0 + nf, 0, e.tid, false); }
     store_all();
     if constexpr (SAC) {
         // ring mode: the launch's last workgroup (a ticket per workgroup, taken after all of its
@@ -2370,7 +2382,8 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
             if (threadIdx.x == 0) {
                 const unsigned long long t = atomicAdd((unsigned long long*)&a.ring_state[2], 1ull);
                 if (t == (unsigned long long)gridDim.x - 1ull) {
-                    const int64_t np = ring_pos0 + N, sz = (int64_t)a.ring_state[1] + N;
+                    const int64_t adv = kCol ? (int64_t)nf * N : N;   // (collect: the launch's steps x N)
+                    const int64_t np = ring_pos0 + adv, sz = (int64_t)a.ring_state[1] + adv;
                     a.ring_state[0] = (long long)(np >= a.ring_cap ? np - a.ring_cap : np);
                     a.ring_state[1] = (long long)(sz > a.ring_cap ? a.ring_cap : sz);
                     a.ring_state[2] = 0;
@@ -2452,7 +2465,13 @@ template <typename R, int PH, bool W, int LPE> void launch_policy_lpe(const Step
 // pd_rollout_sac: one launch of the chain (a.n_fused steps at most), a workgroup per 16 envs
 template <typename R, int PH, bool W> void launch_sac_roll(const StepArgs<R>& a, hipStream_t s) {
     unsigned grid = (unsigned)((a.n * 16 + kStepBlock - 1) / kStepBlock);
-    hipLaunchKernelGGL((k_step<R, PH, 0, W, 16, 0, false, false, true, true>), dim3(grid), dim3(kStepBlock), 0, s, a);
+    hipLaunchKernelGGL((k_step<R, PH, 0, W, 16, 0, false, false, true, kRollEpisodes>), dim3(grid), dim3(kStepBlock), 0, s, a);
+}
+
+// pd_collect_sac: one launch of the chain (a.n_fused collection steps), a workgroup per 16 envs
+template <typename R, int PH, bool W> void launch_sac_collect(const StepArgs<R>& a, hipStream_t s) {
+    unsigned grid = (unsigned)((a.n * 16 + kStepBlock - 1) / kStepBlock);
+    hipLaunchKernelGGL((k_step<R, PH, 0, W, 16, 0, false, false, true, kRollCollect>), dim3(grid), dim3(kStepBlock), 0, s, a);
 }
 
 }  // namespace pd

@@ -456,6 +456,13 @@ template <typename R> void dispatch_sac_roll(const pd_env* e, const StepArgs<R>&
     else { if (w) launch_sac_roll<R, 1, true>(a, s); else launch_sac_roll<R, 1, false>(a, s); }
 }
 
+// and of the SAC collection kernels
+template <typename R> void dispatch_sac_collect(const pd_env* e, const StepArgs<R>& a, hipStream_t s) {
+    const bool w = e->cfg.enable_wind != 0;
+    if (e->cfg.phase == PD_PHASE_PURE_THROTTLE) { if (w) launch_sac_collect<R, 0, true>(a, s); else launch_sac_collect<R, 0, false>(a, s); }
+    else { if (w) launch_sac_collect<R, 1, true>(a, s); else launch_sac_collect<R, 1, false>(a, s); }
+}
+
 template <typename R> void launch_insert(pd_env* e, hipStream_t s) {
     hipLaunchKernelGGL(k_insert<R>, dim3(1), dim3(64), 0, s, e->pend, e->keys_cd, (R*)e->pay_cd, e->logcap_cd,
                        e->keys_cl, (R*)e->pay_cl, e->logcap_cl);
@@ -567,6 +574,35 @@ pd_status rollout_sac_impl(pd_env* e, const SacIO& io, int reset_first, int32_t 
     }
     // (b.fin means "frozen until reset" to the policy rollouts: left clear for whatever follows)
     PD_HIP(hipMemsetAsync(e->fin, 0, N, s));
+    return PD_OK;
+}
+
+// pd_collect_sac: n_steps collection steps (k_step<..., SAC, kRollCollect>) as a chain of launches
+// of at most pd_tuning.step_fuse steps, with no host synchronisation and no allocation.  Each
+// launch's per-step outputs (and, slab mode, its rows) start at the steps already taken; in ring
+// mode every launch reads the ring's position from ring_state and its last workgroup advances it
+template <typename R>
+pd_status collect_sac_impl(pd_env* e, const SacIO& io, int32_t n_steps, void* reward, uint8_t* done, uint8_t* trunc,
+                           int8_t* tid, hipStream_t s) {
+    const size_t N = (size_t)e->cfg.n_envs, A = (size_t)e->act_dim;
+    const size_t W = 2 * (size_t)e->obs_dim + A + 2;
+    const int K = e->tune.step_fuse;
+    for (int32_t t = 0; t < n_steps; t += K) {
+        StepArgs<R> a = make_args<R>(e);
+        a.n_fused = n_steps - t < K ? n_steps - t : K;
+        a.sac_lo = io.lo; a.sac_hi = io.hi; a.sac_max = io.max_action;
+        a.sac_hs = io.head_stride; a.sac_draw = io.draw; a.sac_mlp = io.mlp;
+        a.sac_eps_out = io.eps_out ? io.eps_out + (size_t)t * N * A : nullptr;
+        a.slab = io.ring_state ? io.slab : io.slab + (size_t)t * N * W;
+        a.obs32 = io.obs32;
+        a.ring_cap = io.ring_cap; a.ring_state = io.ring_state; a.prio = io.prio; a.max_prio = io.max_prio;
+        a.reward = reward ? (R*)reward + (size_t)t * N : nullptr;
+        a.done = done ? done + (size_t)t * N : nullptr;
+        a.trunc = trunc ? trunc + (size_t)t * N : nullptr;
+        a.trunc_id = tid ? tid + (size_t)t * N : nullptr;
+        dispatch_sac_collect<R>(e, a, s);
+        PD_HIP(hipGetLastError());
+    }
     return PD_OK;
 }
 
@@ -1100,6 +1136,33 @@ pd_status pd_step_sac_fused(pd_env* e, int32_t state_dim, int32_t action_dim, in
     return sac_step(e, io, stream);
 }
 
+// The checks pd_rollout_sac and pd_collect_sac share (fn: the entry point's name, what: its kernel):
+// an actor the loop kernels' tile holds, on a handle they are instantiated for
+static pd_status sac_loop_check(const pd_env* e, const std::string& fn, const std::string& what, int32_t state_dim,
+                                int32_t action_dim, int32_t hidden, int32_t n_hidden_layers, const float* const* params) {
+    const int S = e->obs_dim, A = e->act_dim;
+    if (state_dim != S || action_dim != A)
+        return fail(PD_ERR_INVALID, fn + ": the actor's state_dim / action_dim differ from the handle's");
+    if (n_hidden_layers < 1 || n_hidden_layers > kSacMaxLayers || A > 8 || S > 16)
+        return fail(PD_ERR_INVALID, fn + ": 1..8 hidden layers, state_dim <= 16, action_dim <= 8");
+    if (hidden == 512)
+        return fail(PD_ERR_UNSUPPORTED, fn + ": hidden width 512 does not fit the " + what + " kernel's LDS tile "
+                                        "(128 or 256; use the per-step path, pd_step_sac_fused)");
+    if (hidden != 128 && hidden != 256) return fail(PD_ERR_UNSUPPORTED, fn + ": hidden width 128 or 256 only");
+    for (int k = 0; k < 2 * (n_hidden_layers + 2); ++k) {
+        if (!params[k]) return fail(PD_ERR_INVALID, fn + ": null parameter");
+        if ((uintptr_t)params[k] % 16 != 0) return fail(PD_ERR_UNSUPPORTED, fn + ": parameter not 16-byte aligned");
+    }
+    if (e->cfg.action_f64) return fail(PD_ERR_UNSUPPORTED, fn + ": float32 actions only (action_f64 = 0)");
+    if (e->cfg.rtd == PD_RTD_PSO || e->cfg.integrator != PD_INTEG_REFERENCE ||
+        (e->cfg.phase != PD_PHASE_PURE_THROTTLE && e->cfg.phase != PD_PHASE_LANDING_BURN))
+        return fail(PD_ERR_UNSUPPORTED, fn + ": the RL landing burns (reference integrator) only");
+    if (e->lpe != 16)
+        return fail(PD_ERR_UNSUPPORTED, fn + ": the handle does not step 16 lanes per env (the workgroup's 16 "
+                                        "envs are the actor's MLP tile; use the per-step path, pd_step_sac_fused)");
+    return PD_OK;
+}
+
 pd_status pd_rollout_sac(pd_env* e, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t n_hidden_layers,
                          const float* const* params, int32_t deterministic, float log_std_min, float log_std_max,
                          float max_action, int32_t reset_first, int32_t max_steps, void* ret, int32_t* steps,
@@ -1107,25 +1170,8 @@ pd_status pd_rollout_sac(pd_env* e, int32_t state_dim, int32_t action_dim, int32
     if (!e || !params) return fail(PD_ERR_INVALID, "pd_rollout_sac: null env/params");
     if (max_steps < 0) return fail(PD_ERR_INVALID, "pd_rollout_sac: max_steps < 0");
     const int S = e->obs_dim, A = e->act_dim;
-    if (state_dim != S || action_dim != A)
-        return fail(PD_ERR_INVALID, "pd_rollout_sac: the actor's state_dim / action_dim differ from the handle's");
-    if (n_hidden_layers < 1 || n_hidden_layers > kSacMaxLayers || A > 8 || S > 16)
-        return fail(PD_ERR_INVALID, "pd_rollout_sac: 1..8 hidden layers, state_dim <= 16, action_dim <= 8");
-    if (hidden == 512)
-        return fail(PD_ERR_UNSUPPORTED, "pd_rollout_sac: hidden width 512 does not fit the rollout kernel's LDS tile "
-                                        "(128 or 256; use the per-step path, pd_step_sac_fused)");
-    if (hidden != 128 && hidden != 256) return fail(PD_ERR_UNSUPPORTED, "pd_rollout_sac: hidden width 128 or 256 only");
-    for (int k = 0; k < 2 * (n_hidden_layers + 2); ++k) {
-        if (!params[k]) return fail(PD_ERR_INVALID, "pd_rollout_sac: null parameter");
-        if ((uintptr_t)params[k] % 16 != 0) return fail(PD_ERR_UNSUPPORTED, "pd_rollout_sac: parameter not 16-byte aligned");
-    }
-    if (e->cfg.action_f64) return fail(PD_ERR_UNSUPPORTED, "pd_rollout_sac: float32 actions only (action_f64 = 0)");
-    if (e->cfg.rtd == PD_RTD_PSO || e->cfg.integrator != PD_INTEG_REFERENCE ||
-        (e->cfg.phase != PD_PHASE_PURE_THROTTLE && e->cfg.phase != PD_PHASE_LANDING_BURN))
-        return fail(PD_ERR_UNSUPPORTED, "pd_rollout_sac: the RL landing burns (reference integrator) only");
-    if (e->lpe != 16)
-        return fail(PD_ERR_UNSUPPORTED, "pd_rollout_sac: the handle does not step 16 lanes per env (the workgroup's 16 "
-                                        "envs are the actor's MLP tile; use the per-step path, pd_step_sac_fused)");
+    if (const pd_status st = sac_loop_check(e, "pd_rollout_sac", "rollout", state_dim, action_dim, hidden, n_hidden_layers, params))
+        return st;
     // the traces are addressed as row base + a 32-bit per-lane byte offset within the row
     if ((uint64_t)e->cfg.n_envs * (uint64_t)A * 4ull >= (1ull << 32))
         return fail(PD_ERR_INVALID, "pd_rollout_sac: n_envs x action_dim x 4 must be below 2^32 bytes");
@@ -1139,6 +1185,50 @@ pd_status pd_rollout_sac(pd_env* e, int32_t state_dim, int32_t action_dim, int32
     return with_real(e, [&](auto r) {
         return rollout_sac_impl<decltype(r)>(e, io, reset_first, max_steps, ret, steps, done, trunc_id, actions_out,
                                              rewards_out, (hipStream_t)stream);
+    });
+}
+
+pd_status pd_collect_sac(pd_env* e, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t n_hidden_layers,
+                         const float* const* params, int32_t deterministic, float log_std_min, float log_std_max,
+                         float max_action, int32_t n_steps, float* ring, int64_t capacity, long long* ring_state,
+                         float* priorities, const float* max_priority, float* obs32, float* eps_out, void* reward,
+                         uint8_t* done, uint8_t* truncated, int8_t* trunc_id, void* stream) {
+    if (!e || !params) return fail(PD_ERR_INVALID, "pd_collect_sac: null env/params");
+    if (n_steps < 0) return fail(PD_ERR_INVALID, "pd_collect_sac: n_steps < 0");
+    const int S = e->obs_dim, A = e->act_dim;
+    if (const pd_status st = sac_loop_check(e, "pd_collect_sac", "collection", state_dim, action_dim, hidden, n_hidden_layers, params))
+        return st;
+    if (n_steps == 0) return PD_OK;   // (nothing to write: ring and the outputs are not looked at)
+    const int64_t N = e->cfg.n_envs;
+    const int64_t W = 2 * (int64_t)S + A + 2;
+    if (!ring) return fail(PD_ERR_INVALID, "pd_collect_sac: null ring");
+    if (ring_state) {
+        // (the rows of one launch must not alias -- its workgroups run at different steps -- and
+        // position + t N + i stays below 2 capacity: one subtraction wraps it)
+        if ((int64_t)n_steps * N > capacity)
+            return fail(PD_ERR_INVALID, "pd_collect_sac: ring mode needs capacity >= n_steps x n_envs");
+        if (capacity * W >= (1ll << 32)) return fail(PD_ERR_INVALID, "pd_collect_sac: capacity x row width must be below 2^32");
+        if (priorities && !max_priority) return fail(PD_ERR_INVALID, "pd_collect_sac: priorities without max_priority");
+    } else if ((int64_t)n_steps * N * W >= (1ll << 32)) {
+        return fail(PD_ERR_INVALID, "pd_collect_sac: n_steps x n_envs x row width must be below 2^32");
+    }
+    // eps_out rows are addressed as row base + a 32-bit per-lane byte offset within the row
+    if ((uint64_t)N * (uint64_t)A * 4ull >= (1ull << 32))
+        return fail(PD_ERR_INVALID, "pd_collect_sac: n_envs x action_dim x 4 must be below 2^32 bytes");
+    PD_HIP(hipSetDevice(e->device));
+    SacIO io{nullptr, nullptr, nullptr, log_std_min, log_std_max, max_action, nullptr, ring, obs32, (uint32_t)(2 * A)};
+    io.draw = deterministic ? 0 : 1;
+    io.eps_out = deterministic ? nullptr : eps_out;
+    io.ring_cap = ring_state ? capacity : 0;
+    io.ring_state = ring_state;
+    io.prio = ring_state ? priorities : nullptr;
+    io.max_prio = max_priority;
+    io.mlp.S = S; io.mlp.L = n_hidden_layers; io.mlp.A = A; io.mlp.H = hidden; io.mlp.obs = nullptr;
+    for (int l = 0; l < n_hidden_layers; ++l) { io.mlp.w[l] = params[2 * l]; io.mlp.b[l] = params[2 * l + 1]; }
+    io.mlp.wm = params[2 * n_hidden_layers]; io.mlp.bm = params[2 * n_hidden_layers + 1];
+    io.mlp.ws = params[2 * n_hidden_layers + 2]; io.mlp.bs = params[2 * n_hidden_layers + 3];
+    return with_real(e, [&](auto r) {
+        return collect_sac_impl<decltype(r)>(e, io, n_steps, reward, done, truncated, trunc_id, (hipStream_t)stream);
     });
 }
 

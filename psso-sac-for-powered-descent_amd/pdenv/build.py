@@ -1,8 +1,8 @@
 """Compile libpdenv.so for gfx950 in-tree (hipcc cross-compiles without a GPU).
 
 The step kernel is instantiated per (precision, phase family, wind) in 12 objects from
-csrc/kstep.hip (plus two RK4 units and the eight SAC rollout units, pd_rollout_sac: each its own
-object, so they build next to the others), compiled in parallel with the two host units -- the
+csrc/kstep.hip (plus two RK4 units, the eight SAC rollout units, pd_rollout_sac, and the eight SAC
+collection units, pd_collect_sac: each its own object, so they build next to the others), compiled in parallel with the two host units -- the
 handle and C ABI (pdenv.hip) and the host table builder (pd_tables.hip: host code only, with the
 same flags, on which the tables' bits depend) -- and the PSO kernels (pdpso.hip) and the SAC actor
 (pdsac.hip), then linked into one shared library.  Objects are rebuilt when any source is newer
@@ -48,6 +48,10 @@ def units():
     for r, ph, w in ((r, ph, w) for r in (0, 1) for ph in (0, 1) for w in (0, 1)):
         u.append((os.path.join(OBJ, f"kstep_r{r}_p{ph}_w{w}_roll.o"), "kstep.hip",
                   [f"-DPD_KR={r}", f"-DPD_KPH={ph}", f"-DPD_KW={w}", "-DPD_KROLL=1"]))
+    # and the SAC collection kernels (pd_collect_sac), the same eight
+    for r, ph, w in ((r, ph, w) for r in (0, 1) for ph in (0, 1) for w in (0, 1)):
+        u.append((os.path.join(OBJ, f"kstep_r{r}_p{ph}_w{w}_collect.o"), "kstep.hip",
+                  [f"-DPD_KR={r}", f"-DPD_KPH={ph}", f"-DPD_KW={w}", "-DPD_KROLL=2"]))
     return [(o, os.path.join(CSRC, s), list(d)) for o, s, d in u]
 
 

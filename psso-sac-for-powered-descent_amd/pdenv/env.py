@@ -428,6 +428,37 @@ class PoweredDescentEnv:
                                         _ptr(tid), _ptr(actions_out), _ptr(rewards_out), _stream(self.device)))
         return ret, steps, done, tid
 
+    def collect_sac(self, kernel, n_steps, deterministic=False, ring=None, capacity=0, ring_state=None, priorities=None,
+                    max_priority=None, obs32=None, eps_out=None, reward=None, done=None, truncated=None, trunc_id=None):
+        """n_steps SAC collection steps of every env in one call (pd_collect_sac): the actor (kernel:
+        a pdenv.sac.ActorKernel) inside the step kernel's fused-step loop, envs auto-resetting per
+        config, the same bits as n_steps step_sac_fused calls.  Step t's transition row of env i
+        goes to ring row (ring_state[0] + t N + i) mod capacity with priorities[row] =
+        max_priority[0], and ring_state advances by n_steps N (n_steps N <= capacity) -- or,
+        ring_state None, into ring as a [n_steps, N, 2S + A + 2] slab.  obs32 [N, S] is an output
+        only: the observation after the last step (the first step's is formed from the handle's
+        state).  eps_out [n_steps, N, A] float32, reward [n_steps, N] (handle precision), done /
+        truncated [n_steps, N] uint8 and trunc_id [n_steps, N] int8, when given, receive every
+        step's values.
+        Needs a handle stepping 16 lanes per env and an actor of hidden width 128 or 256 (PdError,
+        PD_ERR_UNSUPPORTED, otherwise: pdenv.sac.SACCollector.collect then loops the per-step
+        call).  No copies, allocations or syncs."""
+        self._check_steppable()
+        a = kernel.actor
+        K = int(n_steps)
+        for t, shape, dt in ((eps_out, (K, self.n, self.action_dim), torch.float32), (reward, (K, self.n), self.dtype),
+                             (done, (K, self.n), torch.uint8), (truncated, (K, self.n), torch.uint8),
+                             (trunc_id, (K, self.n), torch.int8)):
+            if t is not None and K >= 0 and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()
+                                             or t.device != self.device):
+                raise ValueError(f"per-step output must be a contiguous {dt} {list(shape)} on {self.device}")
+        L.check(self.lib.pd_collect_sac(self.h, kernel.S, kernel.A, kernel.H, kernel.nl, kernel.ptrs(),
+                                        int(bool(deterministic)), float(a.log_std_min), float(a.log_std_max),
+                                        float(a.max_action), K, _ptr(ring), int(capacity), _ptr(ring_state),
+                                        _ptr(priorities), _ptr(max_priority), _ptr(obs32), _ptr(eps_out), _ptr(reward),
+                                        _ptr(done), _ptr(truncated), _ptr(trunc_id), _stream(self.device)))
+        self._steps += max(K, 0)
+
     # ------------------------------------------------------------------ checkpoint / restore
     def checkpoint(self):
         """Every per-env buffer (state, g-load window, actuators, wind, counters, aero caches)

@@ -194,6 +194,14 @@ def gather_slabs(slab, dist=None):
     return out
 
 
+def step_major(gathered):
+    """The ranks' collection slabs [world, k, N, W], as all_gather_into_tensor stacks them, as rows
+    [k * world * N, W] in step-major order: step 0 of every rank in rank order, then step 1, ... --
+    the order k per-step gathers (gather_slabs) append in."""
+    world, k, n, w = gathered.shape
+    return gathered.permute(1, 0, 2, 3).reshape(k * world * n, w)
+
+
 class ActorKernel:
     """The Actor's forward pass as one pd_sac_actor launch (the shared MLP on MFMA and both heads,
     activations in LDS): obs [N, S] float32 -> heads [N, 2A] (mean | log_std, unclamped).  Reads
@@ -264,7 +272,10 @@ class SACCollector:
     each replay.  flush_every > 0: a pd_flush_misses call every that many steps (0, the default:
     none -- the step launch inserts the neighbourhoods it solved itself, ABI 10).
     step() returns the step's transition rows: a view of the replay ring's rows (valid until the
-    ring wraps onto them) in ring mode, else a fresh tensor."""
+    ring wraps onto them) in ring mode, else a fresh tensor.
+    collect(k) is k steps in one call (pd_collect_sac: the actor inside the step kernel's fused-step
+    loop, the span between two learner updates, during which the actor is fixed), the same bits
+    as k step() calls; step() and collect() may alternate.  use_graph applies to step() only."""
 
     def __init__(self, env, actor, buffer=None, dist=None, learner_rank=0, generator=None,
                  deterministic=False, use_graph=False, flush_every=0, fused=True):
@@ -362,6 +373,95 @@ class SACCollector:
             return full
         self.graph.replay()
         return self._finish(self._slab)
+
+    def _step_logged(self, t, outs):
+        """One step() whose reward, done, truncated and trunc_id (handle precision) go to row t of
+        the given tensors: the unfused path's pd_step leaves them in the handle's buffers; the
+        fused calls return the reward only as the row's float32, so the handle is put back
+        (checkpoint, stream-ordered) and pd_step of the step's action gives them, ending in the same
+        state (as _evaluate_per_step does)."""
+        env = self.env
+        if self.fused:
+            blob = env.checkpoint()
+            rows = self.step()
+            env.restore(blob)
+            env.step_raw_noflush(self.action)
+        else:
+            rows = self.step()
+        for out, buf in zip(outs, (env.reward_buf, env.done_buf, env.trunc_buf, env.trunc_id_buf)):
+            if out is not None:
+                out[t].copy_(buf)
+        return rows
+
+    @torch.no_grad()
+    def collect(self, k, rewards=None, done=None, truncated=None, trunc_id=None):
+        """k collection steps of every env; returns the k * N (times the world size) transition
+        rows it appended, in step order: a view of the ring's rows in ring mode (unless they
+        wrap), else a fresh tensor.  One pd_collect_sac call where the library takes it -- a single
+        rank with a buffer writes the ring in place, several ranks write a local [k, N, W] slab,
+        all-gather it and append it in step-major order (step_major) -- and k step() calls, the
+        same values, where it answers PD_ERR_UNSUPPORTED (a handle that does not step 16 lanes per
+        env, hidden 512), for an actor ActorKernel does not cover, with fused=False, and in ring
+        mode when k * N rows do not fit the buffer.  rewards [k, N] (handle precision), done /
+        truncated [k, N] uint8 and trunc_id [k, N] int8, when given, receive every step's values.
+        `obs` is left at the next observation.
+        Cost of the fallback with any of these four outputs given and fused=True: the fused step
+        calls return the reward only as the row's float32, so every step saves a checkpoint, steps,
+        restores it and steps again through pd_step -- two handle copies and a second env step per
+        step, more than twice a plain step().  Without the outputs the fallback is k plain step()
+        calls."""
+        k = int(k)
+        env, b = self.env, self.buffer
+        outs = (rewards, done, truncated, trunc_id)
+        world = self.dist.get_world_size() if self.multi else 1
+        rows = None
+        # (the choice of path must be the same on every rank: only ring mode, a single rank, looks at
+        # the buffer)
+        if self.fused and self.kernel is not None and k > 0 and (not self.ring or k * env.n <= b.capacity):
+            a = self.actor
+            kw = dict(deterministic=self.deterministic, obs32=self.obs, reward=rewards, done=done, truncated=truncated,
+                      trunc_id=trunc_id)
+            slab = None
+            if self.ring:
+                kw.update(ring=b.data, capacity=b.capacity, ring_state=b.state_dev,
+                          priorities=getattr(b, "priorities", None), max_priority=getattr(b, "max_prio_dev", None))
+            else:
+                slab = torch.empty(k, env.n, 2 * env.obs_dim + env.action_dim + 2, dtype=torch.float32, device=self.obs.device)
+                kw.update(ring=slab)
+            try:
+                env.collect_sac(self.kernel, k, **kw)
+            except L.PdError as err:   # (nothing was launched: the per-step loop below)
+                if getattr(err, "status", None) != L.PD_ERR_UNSUPPORTED:
+                    raise
+            else:
+                if self.ring:
+                    start = b.position
+                    b.note_appended(k * env.n)
+                    rows = b.rows(start, k * env.n)
+                else:
+                    if self.multi:
+                        full = torch.empty((world,) + tuple(slab.shape), dtype=slab.dtype, device=slab.device)
+                        self.dist.all_gather_into_tensor(full, slab)
+                        rows = step_major(full)
+                    else:
+                        rows = slab.reshape(k * env.n, slab.shape[2])
+                    if self.rank == self.learner_rank and b is not None:
+                        # (more rows than the buffer holds: step by step, as k step() calls append)
+                        per = rows.shape[0] if rows.shape[0] <= b.capacity else world * env.n
+                        for r0 in range(0, rows.shape[0], per):
+                            b.add_batch(rows[r0:r0 + per])
+                before, self.steps = self.steps, self.steps + k
+                if self.flush_every and self.steps // self.flush_every != before // self.flush_every:
+                    env.flush()
+                return rows
+        W = 2 * env.obs_dim + env.action_dim + 2
+        if k <= 0:
+            return torch.empty(0, W, dtype=torch.float32, device=self.obs.device)
+        # (ring mode: a step's rows are a view the ring may wrap onto before the loop ends)
+        keep = (lambda r: r.clone()) if self.ring else (lambda r: r)
+        if all(o is None for o in outs):
+            return torch.cat([keep(self.step()) for _ in range(k)])
+        return torch.cat([keep(self._step_logged(t, outs)) for t in range(k)])
 
 
 # ---------------------------------------------------------------------------- evaluation rollouts
