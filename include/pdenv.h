@@ -470,6 +470,50 @@ pd_status pd_pso_swarm_minima(int64_t n_particles, int32_t dim, int32_t n_swarms
 pd_status pd_pso_update_bests(int32_t n_swarms, int32_t dim, const double* min_fitness, const double* min_position,
                               double* swarm_best_fitness, double* swarm_best, double* global_best_fitness,
                               double* global_best, void* stream);
+/* Prioritized replay on the device: the learner's sample and priority update of the reference's
+ * PrioritizedReplayBuffer (sac_pytorch.py:90-124) without the host.  No env handle: device pointers,
+ * the current HIP device, no host synchronisation, nothing read back.  (additive exports, ABI 11)
+ *
+ * pd_per_sample draws `batch` distinct items of priorities[0, size) with probability proportional
+ * to priority^alpha, without replacement: the distribution of np.random.choice(size, batch,
+ * replace=False, p=prio**alpha / sum) (sac_pytorch.py:96-101), as an exponential race.
+ *  weight  : w_i = pow((double)priorities[i], alpha); an item takes part only if 0 < w_i < inf
+ *            (a zero, negative or NaN priority is never drawn)
+ *  uniform : one Philox4x32-10 block per pair of items, m = i >> 1: counter {lo32(m), lo32(draw),
+ *            hi32(draw), 48}, key (lo32(seed), hi32(seed)); u_i = 1 - u01(x, y) for even i and
+ *            1 - u01(z, w) for odd i, in (0, 1].  A sample depends on (seed, draw, priorities) only
+ *  key     : e_i = -log(u_i) / w_i in binary64, +inf for an item that takes no part
+ *  indices : [batch] the items with the smallest keys, ties to the lower index, slot j the j-th
+ *            smallest -- the order of numpy's sequential draw
+ *  weights : [batch] float32 (size w_j / sum w)^-beta / (the largest of the batch)
+ *            (sac_pytorch.py:104-108), computed as (w_ref / w_j)^beta in binary64 with w_ref the
+ *            smallest selected weight (the sum over the buffer cancels); the largest is exactly 1
+ *  rows    : [batch][width] = ring[indices[j]] bit for bit (sac_pytorch.py:110-116); ring and rows
+ *            may be NULL
+ *  keys_out: optional [size], receives every e_i
+ *  info    : [4] int32: slots filled = min(batch, finite keys); finite keys; 1 if the internal
+ *            candidate list overflowed (candidates were dropped: never in a correct run); 0.
+ *            Slots past info[0] get index -1, weight 0 and zero rows
+ *  scratch : at least the bytes the scratch-size call below returns for (size, batch), 8-byte
+ *            aligned, owned by the caller; the call initialises what it reads of it
+ * PD_ERR_INVALID for a NULL priorities / indices / weights / info / scratch, size < 1, batch < 1,
+ * batch > size, rows without ring, a ring with width < 1, alpha < 0, a non-finite alpha or beta, a
+ * short or misaligned scratch; PD_ERR_UNSUPPORTED for batch > PD_PER_MAX_BATCH or size >= 2^31;
+ * all before any launch.
+ *
+ * pd_per_update (sac_pytorch.py:120-124): priorities[indices[j]] = fabsf(td_errors[j]) + epsilon
+ * (a float32 add) for every j with 0 <= indices[j] < size -- other indices, the -1 of a short sample
+ * among them, are skipped -- and *max_priority raised to the largest written value that compares
+ * greater (an integer atomic max on the bit pattern: priorities are non-negative; a NaN never raises
+ * it).  Indices are distinct by contract; of duplicates, one written value survives. */
+#define PD_PER_MAX_BATCH 1024
+size_t pd_per_sample_scratch_bytes(int64_t size, int32_t batch);
+pd_status pd_per_sample(const float* priorities, int64_t size, int32_t batch, double alpha, double beta,
+                        uint64_t seed, uint64_t draw, const float* ring, int32_t width, int64_t* indices,
+                        float* weights, float* rows, double* keys_out, int32_t* info, void* scratch,
+                        size_t scratch_bytes, void* stream);
+pd_status pd_per_update(float* priorities, int64_t size, const int64_t* indices, const float* td_errors,
+                        int32_t batch, float epsilon, float* max_priority, void* stream);
 /* Insert the aero neighbourhoods solved on device and still queued into the handle's tables
  * (one tiny kernel; a no-op when nothing is queued).  Since ABI 10 every step launch (pd_step,
  * pd_step_n, pd_step_sac*, pd_rollout) inserts the neighbourhoods it solved itself, by its last

@@ -7,7 +7,7 @@ reward/termination run as HIP kernels in libpdenv.so (C ABI: include/pdenv.h).
 from ._lib import PdError, INFO_FIELDS, load  # noqa: F401
 from .env import PoweredDescentEnv  # noqa: F401
 from .params import Params, load_pack  # noqa: F401
-from .sac import evaluate_agent, summarize_rollout  # noqa: F401
+from .sac import KernelPrioritizedReplayBuffer, evaluate_agent, summarize_rollout  # noqa: F401
 
 __all__ = ["PoweredDescentEnv", "Params", "load_pack", "PdError", "INFO_FIELDS", "load", "evaluate_agent",
-           "summarize_rollout"]
+           "summarize_rollout", "KernelPrioritizedReplayBuffer"]

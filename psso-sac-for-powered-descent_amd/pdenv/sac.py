@@ -177,6 +177,110 @@ class DevicePrioritizedReplayBuffer(DeviceReplayBuffer):
         self.max_prio_dev.fill_(self.max_priority)
 
 
+class KernelPrioritizedReplayBuffer(DevicePrioritizedReplayBuffer):
+    """DevicePrioritizedReplayBuffer with the learner's round trip on the library's kernels: sample
+    is one pd_per_sample call (its own Philox draws keyed by (seed, draw); indices, importance
+    weights and the gathered rows), update_priorities one pd_per_update call that raises the
+    device-side maximum -- neither reads anything back, so a learner update makes no host
+    synchronisation.  max_priority lives on the device (max_prio_dev, which the collection kernels
+    read): reading the property is the one place that synchronises, setting it fills the device
+    value, and add_batch fills the new rows' priorities from the device value.  SACCollector takes
+    the class as it takes its parent.
+
+    sample(batch_size) returns the parent's 7-tuple; the first five are views of one [B, W] tensor.
+    That tensor, the weights, the indices (and the keys) are owned by the buffer and reused: the next
+    sample of the same batch size overwrites them, as the collector's slab is overwritten by its next
+    step -- clone what must outlive it."""
+
+    def __init__(self, capacity, state_dim, action_dim, device, alpha=0.6, beta=0.4,
+                 beta_annealing_steps=100000, epsilon=1e-6, seed=0):
+        super().__init__(capacity, state_dim, action_dim, device, alpha=alpha, beta=beta,
+                         beta_annealing_steps=beta_annealing_steps, epsilon=epsilon)
+        self.lib = L.load()
+        self.seed = int(seed)
+        self.draws = 0                # the default `draw` of the next sample
+        self._out = {}                # batch size -> (indices, weights, rows, info, scratch)
+        self._keys = None
+
+    @property
+    def max_priority(self):
+        return float(self.max_prio_dev.item())
+
+    @max_priority.setter
+    def max_priority(self, value):
+        dev = self.__dict__.get("max_prio_dev")   # (the parent's constructor assigns before it exists)
+        if dev is not None:
+            dev.fill_(float(value))
+
+    def add_batch(self, slab):
+        b = min(slab.shape[0], self.capacity)
+        if self.position + b <= self.capacity:
+            self.priorities[self.position:self.position + b] = self.max_prio_dev
+        else:
+            k = self.capacity - self.position
+            self.priorities[self.position:] = self.max_prio_dev
+            self.priorities[:b - k] = self.max_prio_dev
+        DeviceReplayBuffer.add_batch(self, slab)
+
+    def _buffers(self, b):
+        out = self._out.get(b)
+        if out is None:
+            dev = self.data.device
+            nbytes = int(self.lib.pd_per_sample_scratch_bytes(self.capacity, b))
+            out = (torch.empty(b, dtype=torch.int64, device=dev), torch.empty(b, dtype=torch.float32, device=dev),
+                   torch.empty(b, self.width, dtype=torch.float32, device=dev),
+                   torch.empty(4, dtype=torch.int32, device=dev),
+                   torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev))
+            self._out[b] = out
+        return out
+
+    def sample(self, batch_size, draw=None, check=False, keys=False):
+        """batch_size distinct rows, priority**alpha-proportional without replacement; beta is annealed
+        as in the parent.  draw: the Philox draw number (default: a counter that advances by one per
+        call); the sample depends on (seed, draw, priorities) only.  check=True reads the kernel's
+        info words back (a synchronisation): ValueError when fewer than batch_size rows have a
+        positive priority (numpy's error; without check such a sample ends in index -1, weight 0 and
+        zero rows), RuntimeError on an internal overflow.  keys=True appends the [size] float64 key
+        tensor to the result.  The returned tensors are overwritten by the next sample."""
+        if self.size == 0:
+            return None
+        b = int(batch_size)
+        if b > self.size:
+            raise ValueError(f"cannot take a larger sample ({b}) than the buffer holds ({self.size}) without replacement")
+        idx, w, rows, info, scratch = self._buffers(b)
+        if keys and self._keys is None:
+            self._keys = torch.empty(self.capacity, dtype=torch.float64, device=self.data.device)
+        if draw is None:
+            draw = self.draws
+            self.draws += 1
+        L.check(self.lib.pd_per_sample(_ptr(self.priorities), self.size, b, float(self.alpha), float(self.beta),
+                                       self.seed & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1), _ptr(self.data),
+                                       self.width, _ptr(idx), _ptr(w), _ptr(rows), _ptr(self._keys) if keys else None,
+                                       _ptr(info), _ptr(scratch), scratch.numel() * 8, _stream(self.data.device)))
+        self.beta = min(1.0, self.beta + self.beta_increment)
+        if check:
+            filled, finite, overflow, _ = info.tolist()
+            if overflow:
+                raise RuntimeError("pd_per_sample: the candidate list overflowed")
+            if filled < b:
+                raise ValueError(f"fewer rows with a positive priority ({finite}) than the sample size ({b})")
+        S, A = self.state_dim, self.action_dim
+        out = (rows[:, :S], rows[:, S:S + A], rows[:, S + A:S + A + 1], rows[:, S + A + 1:2 * S + A + 1],
+               rows[:, 2 * S + A + 1:], w.reshape(-1, 1), idx)
+        return out + (self._keys[:self.size],) if keys else out
+
+    def update_priorities(self, indices, td_errors):
+        """sac_pytorch.py:120-124 on the device: priority = |td| + epsilon at the (distinct) indices,
+        the device-side maximum raised; indices outside [0, size) -- the -1 of a short sample -- are
+        skipped."""
+        td = td_errors.detach().reshape(-1).float().contiguous()   # (the kernel takes the absolute value)
+        idx = indices.reshape(-1).to(torch.int64).contiguous()
+        if td.numel() != idx.numel():
+            raise ValueError("update_priorities: as many td errors as indices are required")
+        L.check(self.lib.pd_per_update(_ptr(self.priorities), self.size, _ptr(idx), _ptr(td), int(idx.numel()),
+                                       float(self.epsilon), _ptr(self.max_prio_dev), _stream(self.data.device)))
+
+
 def transition_slab(obs, action, reward, next_obs, done):
     """[N, 2S + A + 2] float32: state | action | reward | next_state | done (done, not truncated,
     as the driver stores it: sac_pytorch_powered_descent.py:170-176)."""
