@@ -405,6 +405,36 @@ __device__ __forceinline__ void inertia(DP<R>& P, R fill, R& x_cog, R& I) {
     I = (P.I_dry + P.m_dry * (t3 * t3)) + ((I_ox + I_f) + mp_t * (t4 * t4));
 }
 
+// inertia() in two parts around its two divisions, for a caller that pairs each with another
+// division of the sub-step (pd_step_impl.h, PD_MERGE bit 1): x_prop = xp_num / xp_den, then
+// x_wet = xw_num / xw_den, then inertia_finish.  The operations are inertia()'s, each on the same
+// operands (the fill products are formed again in each part: the same bits).
+template <typename R>
+__device__ __forceinline__ void inertia_x_prop(DP<R>& P, R fill, R& xp_num, R& xp_den) {
+    R h_ox_t = P.h_ox * fill, h_f_t = P.h_f * fill, m_ox_t = P.m_ox * fill, m_f_t = P.m_f * fill;
+    xp_num = m_ox_t * (P.h_lower + h_ox_t / R(2)) + m_f_t * (P.h_lower + P.h_ox + h_f_t / R(2));
+    xp_den = m_ox_t + m_f_t;
+}
+template <typename R>
+__device__ __forceinline__ void inertia_x_wet(DP<R>& P, R fill, R x_prop, R& xw_num, R& xw_den) {
+    R m_ox_t = P.m_ox * fill, m_f_t = P.m_f * fill;
+    R mp_t = m_ox_t + m_f_t;
+    xw_num = P.m_dry * P.x_dry + mp_t * x_prop;
+    xw_den = P.m_dry + mp_t;
+}
+template <typename R>
+__device__ __forceinline__ void inertia_finish(DP<R>& P, R fill, R x_prop, R x_wet, R& x_cog, R& I) {
+    R h_ox_t = P.h_ox * fill, h_f_t = P.h_f * fill, m_ox_t = P.m_ox * fill, m_f_t = P.m_f * fill;
+    R t1 = P.h_lower + h_ox_t / R(2) - x_prop;
+    R I_ox = R(1.0 / 12) * m_ox_t * (h_ox_t * h_ox_t) + m_ox_t * (t1 * t1);
+    R t2 = P.h_lower + P.h_ox + h_f_t / R(2) - x_prop;
+    R I_f = R(1.0 / 12) * m_f_t * (h_f_t * h_f_t) + m_f_t * (t2 * t2);
+    R mp_t = m_ox_t + m_f_t;
+    R t3 = P.x_dry - x_wet, t4 = x_prop - x_wet;
+    x_cog = x_wet;
+    I = (P.I_dry + P.m_dry * (t3 * t3)) + ((I_ox + I_f) + mp_t * (t4 * t4));
+}
+
 // full_rocket_inertia closure (rocket_dimensions.py:198-241), x_cog_inertia_subrocket_0_lambda of
 // the ascent phases, with its own expression order (x_prop_1 uses the untilded m_1_f and
 // h_ox_1_tilde as written)

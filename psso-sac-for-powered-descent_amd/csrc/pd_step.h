@@ -35,6 +35,16 @@ constexpr int kStepBlock = 256;
 #ifndef PD_WIND_SLOPE
 #define PD_WIND_SLOPE 1
 #endif
+// PD_MERGE (experiment builds): work of the sub-step loop that a 2-lane binary64 kernel issued on
+// both lanes of an env's pair, shared -- the same operations on the same operands, so the same
+// bits.  Bit 1 (value 2, the product): the sub-step's seven true divisions run as four division
+// sequences, not five (Mach with inertia's x_prop, x_wet with the gravity ratio, F_x / m with
+// F_y / m, M_z / I alone).  The counting instantiation (CNT) keeps the five sequences, a second
+// implementation on the same device (tests/test_gpu_merge.py).  Bit 0 (value 1) is the merged
+// piece evaluator of tools/experiments/merge_pieces.patch: slower, not kept.
+#ifndef PD_MERGE
+#define PD_MERGE 2
+#endif
 template <typename R, int PHASE, bool WIND, int LPE, int POL, bool RK4, bool SAC> constexpr bool step_big() {
     return PD_WG512 != 0 && sizeof(R) == 8 && PHASE == 0 && WIND && LPE == 2 && POL == 0 && !RK4 && !SAC;
 }

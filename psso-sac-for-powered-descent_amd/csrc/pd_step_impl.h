@@ -1304,6 +1304,12 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
     // kernels are in the same two reports)
     constexpr bool kActAhead = (PD_CARRY & 4) != 0 && !POL && !SAC &&
                                (PD_CARRY_WIDE || (PHASE == 0 && sizeof(R) == 8 && !kSpills));
+    // PD_MERGE bit 1 (pd_step.h): the 2-lane binary64 plain-action kernels whose sub-step calls
+    // inertia() (the two landing burns), outside the RK4 and SAC kernels, which keep their code, and
+    // the policy kernels, which it made longer and c4 3.4 % slower; never the counting
+    // instantiation, which keeps the five division sequences as the reference arrangement.
+    constexpr bool kMergeDiv = (PD_MERGE & 2) != 0 && !CNT && LPE == 2 && sizeof(R) == 8 && PHASE <= 1 && !RK4 && !SAC &&
+                               !POL;
     // LPE != 2: pieces for the trusted queries (rbf) where they fit the register file without
     // spilling (no wind, no RK4, not the landing-burn SAC kernel): c2, c5, the policy sweep
     // the tabulated atmosphere where it pays: binary32 handles and the windless kernels (c2, c4,
@@ -1614,7 +1620,20 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
         }
         const R spR = (R)speed;
         R mach = R(0);
-        if (asnd != R(0)) { R mr = spR / asnd; mach = (R(10) < mr) ? R(10) : mr; }
+        R x_prop = R(0);   // (kMergeDiv: inertia()'s first quotient, needed after the tables)
+        if constexpr (kMergeDiv) {
+            // speed / asnd on the env's even lane with inertia()'s x_prop on its odd lane: both need
+            // only the sub-step's start state.  With asnd 0 the even lane's quotient is inf or NaN
+            // and is not used (mach stays 0, as without the pairing)
+            R fpc0 = div_known<R>((R)(P.m_prop0 - mp), P.m_prop0, P.inv_m_prop0, P.div2 & kDiv2MProp0);
+            if (fpc0 == R(0)) fpc0 = R(1e-6);
+            R xp_num, xp_den, mr;
+            inertia_x_prop<R>(P, R(1) - fpc0, xp_num, xp_den);
+            div_pair<LPE, R>(spR, asnd, xp_num, xp_den, role, mr, x_prop);
+            if (asnd != R(0)) mach = (R(10) < mr) ? R(10) : mr;
+        } else {
+            if (asnd != R(0)) { R mr = spR / asnd; mach = (R(10) < mr) ? R(10) : mr; }
+        }
         // alpha_effective (rockets_physics.py:498-501) and Mach feed the aero tables; what the
         // tables do not need is computed after them (fewer values live across the RBF)
         const R ae = (R)((vy < RS(0)) ? ga - th - Cst<RS>::pi : al);
@@ -1731,12 +1750,25 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
         PD_T(t_aero1);
         PD_ACC(3, t_aero1 - t_aero0);
         R q = R(0.5) * rho * (spR * spR);
-        R fpc = div_known<R>((R)(P.m_prop0 - mp), P.m_prop0, P.inv_m_prop0, P.div2 & kDiv2MProp0);
+        // (kMergeDiv: formed again from a laundered copy of the propellant mass, so that only x_prop
+        // lives across the tables, not the fill products the compiler would share with its head)
+        RS mp_l = mp;
+        if constexpr (kMergeDiv) asm volatile("" : "+v"(mp_l));
+        R fpc = div_known<R>((R)(P.m_prop0 - mp_l), P.m_prop0, P.inv_m_prop0, P.div2 & kDiv2MProp0);
         if (fpc == R(0)) fpc = R(1e-6);
         R x_cog, I;
         // subrocket_0 (full rocket) closures for the ascent, subrocket_2 after (:748-750, :772-774)
-        if (ascent) inertia_full<R>(P, R(1) - fpc, x_cog, I);
-        else inertia<R>(P, R(1) - fpc, x_cog, I);
+        R grq_m = R(0);   // (kMergeDiv: the gravity ratio, paired with x_wet)
+        if constexpr (kMergeDiv) {
+            // inertia()'s x_wet on the even lane with grav_R / (grav_R + y) on the odd lane
+            R xw_num, xw_den, x_wet;
+            inertia_x_wet<R>(P, R(1) - fpc, x_prop, xw_num, xw_den);
+            div_pair<LPE, R>(xw_num, xw_den, P.grav_R, P.grav_R + (R)y, role, x_wet, grq_m);
+            inertia_finish<R>(P, R(1) - fpc, x_prop, x_wet, x_cog, I);
+        } else {
+            if (ascent) inertia_full<R>(P, R(1) - fpc, x_cog, I);
+            else inertia<R>(P, R(1) - fpc, x_cog, I);
+        }
         R d_thrust = x_cog + P.engine_height;
         R d_cp_cg = x_cog - (ascent ? P.cop_ascent : P.cop);
         if constexpr (LPE != 2) wind_block();
@@ -1987,7 +2019,8 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
         PD_T(t_p4); acc_[9 + 7] += t_p4 - t_p3;
 #endif
         div_pair<LPE, R>(fx, (R)m, fy, (R)m, role, vxd, vyq);
-        div_pair<LPE, R>(mz, I, P.grav_R, P.grav_R + (R)y, role, thdd, grq);
+        if constexpr (kMergeDiv) { thdd = mz / I; grq = grq_m; }   // (the gravity ratio went with x_wet)
+        else div_pair<LPE, R>(mz, I, P.grav_R, P.grav_R + (R)y, role, thdd, grq);
         const R gr = P.grav_g0 * (grq * grq);
         const R vyd = vyq - gr;
         if constexpr (RK4) {

@@ -129,7 +129,10 @@ def build_variant(name, defines, unit=(0, 0, 1), patch=None, host=False):
         src = os.path.join(tmp, "p", "csrc", "kstep.hip")
     hobjs = {f"{n}.o": os.path.join(odir, f"{n}.o") for n in HOST_UNITS} if host else {}
     try:
-        _compile((obj, src, [f"-DPD_KR={r}", f"-DPD_KPH={ph}", f"-DPD_KW={w}"] + list(defines)), False)
+        # (with the unit's own flags, KSTEP_FLAGS: without them an all-off variant of the c3 unit is
+        # not the product's schedule and times about 1 % slower than it)
+        _compile((obj, src, [f"-DPD_KR={r}", f"-DPD_KPH={ph}", f"-DPD_KW={w}"] + KSTEP_FLAGS.get((r, ph, w), [])
+                  + list(defines)), False)
         for o in hobjs.values():
             _compile((o, os.path.join(os.path.dirname(src), os.path.basename(o)[:-2] + ".hip"), list(defines)), False)
     finally:
