@@ -514,6 +514,62 @@ pd_status pd_per_sample(const float* priorities, int64_t size, int32_t batch, do
                         size_t scratch_bytes, void* stream);
 pd_status pd_per_update(float* priorities, int64_t size, const int64_t* indices, const float* td_errors,
                         int32_t batch, float epsilon, float* max_priority, void* stream);
+/* The inference-only third of the SAC update on the device (additive exports, ABI 11).  No env
+ * handle: device pointers, the current HIP device, no host synchronisation, nothing read back.
+ *
+ * pd_sac_critic: Critic.forward (sac_pytorch.py:181-221) for n rows in one launch: q [n][2], Q1 in
+ * column 0 and Q2 in column 1, of cat([state, action]); each net Linear(S + A, H) ReLU,
+ * (n_hidden_layers - 1) x [Linear(H, H) ReLU], Linear(H, 1), float32 throughout, on pd_sac_actor's
+ * code (MFMA hidden layers, activations in LDS), the two nets in workgroups of their own.
+ * states [n][S], actions [n][A]; params_q1 / params_q2: host arrays of 2 (n_hidden_layers + 1)
+ * device pointers each, the torch parameters of q1 / q2 in named_parameters() order.
+ * state_dim >= 1, action_dim >= 1, state_dim + action_dim <= 16, n_hidden_layers 1..8, n >= 0, no
+ * null pointer (else PD_ERR_INVALID); hidden 128, 256 or 512 and every parameter 16-byte aligned
+ * (else PD_ERR_UNSUPPORTED); all before any launch.  n = 0: PD_OK without a launch (states,
+ * actions and q may be NULL then). */
+pd_status pd_sac_critic(int64_t n, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t n_hidden_layers,
+                        const float* states, const float* actions, const float* const* params_q1,
+                        const float* const* params_q2, float* q, void* stream);
+/* pd_sac_td_target: the torch.no_grad() block of SACPyTorch.update (sac_pytorch.py:439-443) for a
+ * sampled batch in ONE launch:
+ *     next_actions, next_log_probs = actor.sample(next_states)
+ *     next_q1, next_q2 = critic_target(next_states, next_actions)
+ *     next_q = min(next_q1, next_q2) - alpha * next_log_probs
+ *     target_q = rewards + (1 - dones) * gamma * next_q
+ *  rows    : [batch][width], the replay buffers' row layout state | action | reward | next_state |
+ *            done, width = 2 state_dim + action_dim + 2 (any other width: PD_ERR_INVALID), as
+ *            pd_per_sample leaves them; read once
+ *  actor   : actor_hidden, actor_layers, actor_params as pd_sac_actor's hidden, n_hidden_layers and
+ *            params; log_std_min, log_std_max, max_action as pd_step_sac_ring's
+ *  critic  : critic_hidden, critic_layers, params_q1, params_q2 as pd_sac_critic's (the TARGET critic)
+ *  log_alpha: a device scalar; alpha = expf(*log_alpha), read by the kernel
+ *  eps     : eps_in [batch][A], or NULL: drawn in the kernel, Philox4x32-10 with key (lo32(seed),
+ *            hi32(seed)) and counter {lo32(row), lo32(draw), hi32(draw), 64 + k / 2}, components 2m
+ *            and 2m + 1 of a row from one block by Box-Muller in binary64 (u1 = 1 - u01(x, y),
+ *            u2 = u01(z, w), sqrt(-2 log u1) (cos, sin)(2 pi u2)), cast to float32: a draw depends on
+ *            (seed, draw, row, k) only
+ * In float32, in torch's operation order:
+ *  heads   = Actor.forward(next_state), unclamped: pd_sac_actor's bits on the same rows
+ *  ls = clamp(log_std, min, max), sd = expf(ls), x = mean + sd eps, a = tanhf(x),
+ *  next_actions = a max_action (Actor.sample, sac_pytorch.py:166-179)
+ *  next_log_prob = sum over k ascending of -((x - mean)^2) / (2 sd^2) - ls - log(sqrt(2 pi))
+ *            - logf(1 - a^2 + 1e-6f)   (Normal.log_prob and the tanh correction, :173-177)
+ *  next_q  = [batch][2]: pd_sac_critic's bits on (next_state, next_actions)
+ *  target_q = reward + ((1 - done) gamma) (fminf(q1, q2) - alpha next_log_prob)   [batch]; no
+ *            special case for done = 1 with a non-finite next_q (torch has none)
+ * target_q is required; next_actions [batch][A], next_log_prob [batch], next_q [batch][2], heads
+ * [batch][2A] and eps_out [batch][A] may each be NULL.  Any batch >= 0 (0: PD_OK without a launch).
+ * PD_ERR_INVALID for a negative batch, a dimension below 1, a wrong width or a null rows / target_q
+ * (batch > 0) / log_alpha / parameter; PD_ERR_UNSUPPORTED for shapes outside the two nets' domains
+ * (state_dim + action_dim > 16, action_dim > 8, layers outside 1..8, a hidden width other than 128,
+ * 256, 512, a parameter not 16-byte aligned); all before any launch. */
+pd_status pd_sac_td_target(int64_t batch, int32_t state_dim, int32_t action_dim, const float* rows, int32_t width,
+                           int32_t actor_hidden, int32_t actor_layers, const float* const* actor_params,
+                           float log_std_min, float log_std_max, float max_action, int32_t critic_hidden,
+                           int32_t critic_layers, const float* const* params_q1, const float* const* params_q2,
+                           const float* log_alpha, float gamma, uint64_t seed, uint64_t draw, const float* eps_in,
+                           float* target_q, float* next_actions, float* next_log_prob, float* next_q, float* heads,
+                           float* eps_out, void* stream);
 /* Insert the aero neighbourhoods solved on device and still queued into the handle's tables
  * (one tiny kernel; a no-op when nothing is queued).  Since ABI 10 every step launch (pd_step,
  * pd_step_n, pd_step_sac*, pd_rollout) inserts the neighbourhoods it solved itself, by its last

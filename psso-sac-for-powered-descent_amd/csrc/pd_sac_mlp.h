@@ -1,6 +1,8 @@
 // pd_sac_mlp.h -- the SAC actor's forward pass for one tile of 16 envs by one 256-thread
 // workgroup (SURVEY 8f rank 3's caller).  Used by pd_sac_actor (pdsac.hip, its own launch) and by
-// the c5 step kernel's prologue (k_step<..., SAC>, pd_step_sac_fused: one launch per step).
+// the c5 step kernel's prologue (k_step<..., SAC>, pd_step_sac_fused: one launch per step); and,
+// for the actor and for the twin critic's Q nets (SacQNet below), by pdsactd.hip's pd_sac_critic
+// and pd_sac_td_target.
 //
 // Actor.forward (sac_pytorch.py:129-159): shared_net = Linear(S, H) ReLU [Linear(H, H) ReLU] x
 // (n_hidden_layers - 1), then the mean and log_std heads Linear(H, A) (the clamp of log_std and
@@ -54,6 +56,14 @@ struct SacMlp {
     const float* ws; const float* bs;    // log_std head
 };
 
+// A Q net of the twin critic (Critic.q1 / q2, sac_pytorch.py:181-221): the same Linear-ReLU stack
+// with S = state_dim + action_dim inputs and ONE output, Linear(H, 1), in wm / bm (A = 1; ws, bs
+// unused).  sac_mlp_tile computes A outputs for it instead of the actor's 2A.
+struct SacQNet : SacMlp {};
+template <typename MA> struct sac_head_sets { static constexpr int value = 2; };   // mean and log_std
+template <> struct sac_head_sets<SacQNet> { static constexpr int value = 1; };
+template <> struct sac_head_sets<const SacQNet> { static constexpr int value = 1; };
+
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // LDS floats the tile needs: two activation buffers of 16 rows, row pitch H + 4 (rows start 4
@@ -63,7 +73,7 @@ template <int H> constexpr int sac_mlp_lds_floats() {
 }
 
 // Envs e0 .. e0 + 15 (rows past n read a zero observation); put(e, o, v): head output o
-// (0 .. A-1 mean, A .. 2A-1 log_std, unclamped) of tile row e.  Called by all 256 threads of
+// (0 .. A-1 mean, A .. 2A-1 log_std, unclamped; a SacQNet: o = 0, the Q value) of tile row e.  Called by all 256 threads of
 // the workgroup (it synchronises them); hb: sac_mlp_lds_floats<H>() floats of LDS (a __shared__
 // array: the LDS DMA of the hidden layers addresses it as LDS).  MA: SacMlp
 // in any address space (the step kernel reads it from its kernarg segment).  mark(k): called by
@@ -81,23 +91,24 @@ __device__ __forceinline__ void sac_mlp_tile(const MA& a, int64_t n, int64_t e0,
     float* h1 = hb + kSacTile * P;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int S = a.S, A = a.A;
+    const int NO = sac_head_sets<MA>::value * A;   // head outputs: 2A (the actor), A (a Q net)
     // ---- the heads' weights of this thread's part (env e = tid / 16, part p = tid % 16: k in
     // [p H/16, (p + 1) H/16) of each of the 2A outputs), requested first and held through the
     // hidden layers when the 2A outputs' KP floats fit kHeadRegs (c5: 2 x 16); else read where used
     constexpr int KP = H / 16;
     constexpr int kHeadRegs = 32;
     constexpr int kMaxO = kHeadRegs / KP > 0 ? kHeadRegs / KP : 1;
-    const bool heads_early = 2 * A <= kHeadRegs / KP;
+    const bool heads_early = NO <= kHeadRegs / KP;
     const int e = tid >> 4, p = tid & 15;
     f32x4 hw[kHeadRegs / 4];
     float hb_bias[kMaxO];
 #pragma unroll
-    for (int o = 0; o < kMaxO; ++o) hb_bias[o] = (heads_early && o < 2 * A) ? (o < A ? a.bm[o] : a.bs[o - A]) : 0.f;
+    for (int o = 0; o < kMaxO; ++o) hb_bias[o] = (heads_early && o < NO) ? (o < A ? a.bm[o] : a.bs[o - A]) : 0.f;
 #pragma unroll
     for (int v = 0; v < kHeadRegs / 4; ++v) {
         const int o = (4 * v) / KP, k = (4 * v) % KP;   // (KP is a multiple of 4)
         hw[v] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (heads_early && o < 2 * A)
+        if (heads_early && o < NO)
             hw[v] = *(const f32x4*)((o < A ? a.wm + (size_t)o * H : a.ws + (size_t)(o - A) * H) + p * KP + k);
     }
     // ---- layer 1: h[e][j] = relu(sum_k obs[e][k] W1[j][k] + b1[j]) (k ascending, then the
@@ -241,9 +252,9 @@ __device__ __forceinline__ void sac_mlp_tile(const MA& a, int64_t n, int64_t e0,
         }
 #pragma unroll
         for (int o = 0; o < kMaxO; ++o)
-            if (o < 2 * A) finish(o, so[o], hb_bias[o]);
+            if (o < NO) finish(o, so[o], hb_bias[o]);
     } else {
-        for (int o = 0; o < 2 * A; ++o) {
+        for (int o = 0; o < NO; ++o) {
             const float* wr = (o < A ? a.wm + (size_t)o * H : a.ws + (size_t)(o - A) * H) + p * KP;
             float s = 0.f;
 #pragma unroll 4

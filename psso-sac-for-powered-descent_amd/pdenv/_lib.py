@@ -102,7 +102,7 @@ EXPORTS = ["pd_abi_version", "pd_sizeof_params", "pd_sizeof_config", "pd_last_er
            "pd_step_sac_ring", "pd_sac_actor", "pd_step_sac_fused", "pd_atm_table", "pd_set_tuning", "pd_get_tuning",
            "pd_pso_swarm_minima_scratch_bytes", "pd_step_n_info", "pd_pso_step_chunked", "pd_rollout_policy_chunked",
            "pd_rollout_sac", "pd_atm_table_lds", "pd_wind_slopes", "pd_collect_sac", "pd_per_sample_scratch_bytes",
-           "pd_per_sample", "pd_per_update"]
+           "pd_per_sample", "pd_per_update", "pd_sac_critic", "pd_sac_td_target"]
 PER_MAX_BATCH = 1024              # PD_PER_MAX_BATCH
 ABI_VERSION = 11
 
@@ -151,6 +151,11 @@ def load(path=None):
     L.pd_per_sample.restype = C.c_int
     L.pd_per_update.argtypes = [vp, I64, vp, vp, I32, F32, vp, vp]
     L.pd_per_update.restype = C.c_int
+    L.pd_sac_critic.argtypes = [I64, I32, I32, I32, I32, vp, vp, vp, vp, vp, vp]
+    L.pd_sac_critic.restype = C.c_int
+    L.pd_sac_td_target.argtypes = [I64, I32, I32, vp, I32, I32, I32, vp, F32, F32, F32, I32, I32, vp, vp, vp, F32,
+                                   U64, U64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pd_sac_td_target.restype = C.c_int
     L.pd_set_tuning.argtypes = [vp, P(PdTuning)]
     L.pd_get_tuning.argtypes = [vp, P(PdTuning)]
     L.pd_rollout.argtypes = [vp, vp, I32, vp, vp]

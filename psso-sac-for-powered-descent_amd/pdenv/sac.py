@@ -63,6 +63,7 @@ class DeviceReplayBuffer:
         self.data = torch.zeros(self.capacity, self.width, dtype=torch.float32, device=device)
         self.position = 0
         self.size = 0
+        self.last_rows = None       # the [B, W] rows of the last sample
         # the ring's position and size on the device (int64: position, size, pd_step_sac_ring's
         # workgroup counter): the collection kernel writes its rows there and advances them, the
         # host mirrors (position, size) by note_appended
@@ -115,6 +116,7 @@ class DeviceReplayBuffer:
         """Uniform indices in [0, size) (np.random.randint, sac_pytorch.py:37-46)."""
         idx = torch.randint(0, self.size, (batch_size,), device=self.data.device, generator=generator)
         d = self.data[idx]
+        self.last_rows = d          # the [B, W] tensor behind the views (TdTarget's input)
         S, A = self.state_dim, self.action_dim
         return (d[:, :S], d[:, S:S + A], d[:, S + A:S + A + 1], d[:, S + A + 1:2 * S + A + 1],
                 d[:, 2 * S + A + 1:])
@@ -165,6 +167,7 @@ class DevicePrioritizedReplayBuffer(DeviceReplayBuffer):
         w = (w / w.max()).float().reshape(-1, 1)
         self.beta = min(1.0, self.beta + self.beta_increment)
         d = self.data[idx]
+        self.last_rows = d
         S, A = self.state_dim, self.action_dim
         return (d[:, :S], d[:, S:S + A], d[:, S + A:S + A + 1], d[:, S + A + 1:2 * S + A + 1],
                 d[:, 2 * S + A + 1:], w, idx)
@@ -264,6 +267,7 @@ class KernelPrioritizedReplayBuffer(DevicePrioritizedReplayBuffer):
                 raise RuntimeError("pd_per_sample: the candidate list overflowed")
             if filled < b:
                 raise ValueError(f"fewer rows with a positive priority ({finite}) than the sample size ({b})")
+        self.last_rows = rows
         S, A = self.state_dim, self.action_dim
         out = (rows[:, :S], rows[:, S:S + A], rows[:, S + A:S + A + 1], rows[:, S + A + 1:2 * S + A + 1],
                rows[:, 2 * S + A + 1:], w.reshape(-1, 1), idx)
@@ -349,6 +353,212 @@ class ActorKernel:
         L.check(self.lib.pd_sac_actor(int(obs.shape[0]), self.S, self.H, self.nl, self.A, _ptr(obs), self.ptrs(),
                                       _ptr(heads), _stream(obs.device)))
         return heads
+
+
+class Critic(nn.Module):
+    """sac_pytorch.py:181-221: twin Q nets on cat([state, action]), each Linear(S + A, H) ReLU,
+    (Linear(H, H) ReLU) x (n_hidden_layers - 1), Linear(H, 1).  The members are named q1 / q2, so a
+    reference checkpoint's critic / critic_target state dict loads (keys q1.0.weight ...)."""
+
+    def __init__(self, state_dim, action_dim, hidden_dim=256, n_hidden_layers=2):
+        super().__init__()
+
+        def net():
+            layers = [nn.Linear(state_dim + action_dim, hidden_dim), nn.ReLU()]
+            for _ in range(n_hidden_layers - 1):
+                layers += [nn.Linear(hidden_dim, hidden_dim), nn.ReLU()]
+            return nn.Sequential(*layers, nn.Linear(hidden_dim, 1))
+
+        self.state_dim, self.action_dim = state_dim, action_dim
+        self.q1, self.q2 = net(), net()
+
+    def forward(self, state, action):
+        sa = torch.cat([state, action], dim=1)
+        return self.q1(sa), self.q2(sa)
+
+
+def _q_linears(net):
+    """(hidden Linear layers, output Linear, whether the stack is Linear-ReLU ... Linear(H, 1))."""
+    mods = list(net)
+    lins = [m for m in mods if isinstance(m, nn.Linear)]
+    ok = (len(mods) == 2 * len(lins) - 1 and len(lins) >= 2
+          and all(isinstance(m, nn.Linear if k % 2 == 0 else nn.ReLU) for k, m in enumerate(mods)))
+    return lins[:-1], (lins[-1] if lins else None), ok
+
+
+class CriticKernel:
+    """The Critic's forward pass as one pd_sac_critic launch (Q1 and Q2 in workgroups of their own,
+    ActorKernel's MLP code): states [N, S], actions [N, A] float32 -> out [N, 2] (Q1 | Q2).  Reads the
+    parameter tensors in place, so a Polyak update by `target_param.data.copy_` is seen by the next
+    call.  supported(critic): both nets Linear-ReLU stacks of equal shape, hidden 128/256/512, <= 8
+    hidden layers, S + A <= 16, contiguous float32 parameters on the device, 16-byte aligned."""
+
+    def __init__(self, critic):
+        self.critic = critic
+        self.lib = L.load()
+        self.params = []
+        for net in (critic.q1, critic.q2):
+            hidden, last, _ = _q_linears(net)
+            self.params.append([t for m in hidden + [last] for t in (m.weight, m.bias)])
+        hidden = _q_linears(critic.q1)[0]
+        self.D, self.H, self.nl = hidden[0].in_features, hidden[0].out_features, len(hidden)
+        self._ptrs = tuple((C.c_void_p * len(p))() for p in self.params)
+
+    @staticmethod
+    def supported(critic):
+        shapes = []
+        for net in (critic.q1, critic.q2):
+            hidden, last, ok = _q_linears(net)
+            if not ok or len(hidden) > 8:
+                return False
+            H = hidden[0].out_features
+            ps = [p for m in hidden + [last] for p in (m.weight, m.bias)]
+            if not (H in (128, 256, 512) and 2 <= hidden[0].in_features <= 16 and last.out_features == 1
+                    and last.in_features == H and all(m.in_features == H and m.out_features == H for m in hidden[1:])
+                    and all(p.dtype == torch.float32 and p.is_cuda and p.is_contiguous() and p.data_ptr() % 16 == 0
+                            for p in ps)):
+                return False
+            shapes.append((hidden[0].in_features, H, len(hidden)))
+        return shapes[0] == shapes[1]
+
+    def ptrs(self):
+        """(params_q1, params_q2) as pd_sac_critic / pd_sac_td_target take them (read now)."""
+        for arr, ps in zip(self._ptrs, self.params):
+            for k, t in enumerate(ps):
+                arr[k] = t.data_ptr()
+        return self._ptrs
+
+    def __call__(self, states, actions, out):
+        S, A = int(states.shape[1]), int(actions.shape[1])
+        if S + A != self.D:
+            raise ValueError(f"state_dim + action_dim = {S + A}, the critic takes {self.D}")
+        p1, p2 = self.ptrs()
+        L.check(self.lib.pd_sac_critic(int(states.shape[0]), S, A, self.H, self.nl, _ptr(states), _ptr(actions), p1, p2,
+                                       _ptr(out), _stream(states.device)))
+        return out
+
+
+_TAG_TD_EPS = 64                  # kTagTdEps (csrc/pd_common.h)
+
+
+def td_eps(seed, draw, batch, action_dim, device):
+    """pd_sac_td_target's eps draws [batch, A] as torch expressions (the fallback's eps source):
+    the same Philox4x32-10 blocks and the same Box-Muller in binary64 (torch's log, cos and sin in
+    place of the kernel's), cast to float32 -- the kernel's values to float32 rounding."""
+    i64 = dict(dtype=torch.int64, device=device)
+    mask = 0xFFFFFFFF
+    pairs = (action_dim + 1) // 2
+    row = torch.arange(batch, **i64)[:, None].expand(batch, pairs)
+    c = [row & mask, torch.full_like(row, draw & mask), torch.full_like(row, (draw >> 32) & mask),
+         (_TAG_TD_EPS + torch.arange(pairs, **i64))[None, :].expand(batch, pairs)]
+    k0, k1 = seed & mask, (seed >> 32) & mask
+    for _ in range(10):                                    # (int64 products wrap: the low 64 bits are exact)
+        p0, p1 = c[0] * 0xD2511F53, c[2] * 0xCD9E8D57
+        c = [((p1 >> 32) & mask) ^ c[1] ^ k0, p1 & mask, ((p0 >> 32) & mask) ^ c[3] ^ k1, p0 & mask]
+        k0, k1 = (k0 + 0x9E3779B9) & mask, (k1 + 0xBB67AE85) & mask
+
+    def u01(hi, lo):
+        return ((hi >> 5).double() * 67108864.0 + (lo >> 6).double()) * (1.0 / 9007199254740992.0)
+
+    u1, u2 = 1.0 - u01(c[0], c[1]), u01(c[2], c[3])
+    rho = torch.sqrt(-2.0 * torch.log(u1))
+    ang = 6.283185307179586 * u2
+    z = torch.stack([rho * torch.cos(ang), rho * torch.sin(ang)], dim=2).reshape(batch, 2 * pairs)
+    return z[:, :action_dim].float().contiguous()
+
+
+class TdTarget:
+    """The torch.no_grad() block of SACPyTorch.update (sac_pytorch.py:439-443) as one launch,
+    pd_sac_td_target: actor.sample(next_states), critic_target(next_states, next_actions),
+    min(q1, q2) - alpha * log_prob and rewards + (1 - dones) * gamma * next_q, from the [B, W] rows
+    behind a buffer's sample (`buffer.last_rows`: state | action | reward | next_state | done).
+    log_alpha is the learner's device tensor: the kernel reads it, so the temperature the optimizer
+    just stepped is used without a host read; the nets' parameters are read in place (a Polyak
+    `copy_` into the target critic is seen by the next call).  No host synchronisation.
+
+    __call__(rows, out=None, draw=None, eps=None, next_actions=None, next_log_prob=None, next_q=None,
+    heads=None, eps_out=None) -> target_q [B, 1] (`out`, [B] or [B, 1] float32, when given; else a
+    tensor the object owns per batch size, overwritten by the next call).  eps [B, A]: the rsample
+    noise; None: drawn in the kernel from (seed, draw, row, component), draw defaulting to a counter
+    that advances by one per call.  The optional outputs receive the intermediate values.
+    Where supported() is false (a net outside the kernels' shapes) the same block is evaluated with
+    torch on the same eps source (td_eps), so callers need no branch."""
+
+    def __init__(self, actor, critic_target, log_alpha, gamma, seed=0):
+        self.actor, self.critic, self.log_alpha = actor, critic_target, log_alpha
+        self.gamma, self.seed = float(gamma), int(seed)
+        self.draws = 0
+        self._out = {}
+        self.kernel = self.supported(actor, critic_target, log_alpha)
+        if self.kernel:
+            self.lib = L.load()
+            self.ak, self.ck = ActorKernel(actor), CriticKernel(critic_target)
+
+    @staticmethod
+    def supported(actor, critic, log_alpha):
+        if not (ActorKernel.supported(actor) and CriticKernel.supported(critic)):
+            return False
+        S, A = actor.shared_net[0].in_features, actor.mean.out_features
+        return (critic.q1[0].in_features == S + A and log_alpha.dtype == torch.float32 and log_alpha.is_cuda
+                and log_alpha.numel() == 1)
+
+    def ptrs(self):
+        """(actor_params, params_q1, params_q2) as pd_sac_td_target takes them."""
+        return (self.ak.ptrs(),) + tuple(self.ck.ptrs())
+
+    @torch.no_grad()
+    def _torch(self, rows, eps, outs):
+        a = self.actor
+        S, A = a.shared_net[0].in_features, a.mean.out_features
+        reward, ns, done = rows[:, S + A:S + A + 1], rows[:, S + A + 1:2 * S + A + 1], rows[:, 2 * S + A + 1:]
+        f = a.shared_net(ns)
+        mean, raw = a.mean(f), a.log_std(f)
+        ls = torch.clamp(raw, a.log_std_min, a.log_std_max)
+        sd = ls.exp()
+        x = mean + sd * eps
+        act = torch.tanh(x)
+        lp = (-((x - mean) ** 2) / (2 * sd ** 2) - ls - 0.9189385332046727
+              - torch.log(1 - act.pow(2) + 1e-6)).sum(-1, keepdim=True)
+        na = act * a.max_action
+        q1, q2 = self.critic(ns, na)
+        next_q = torch.min(q1, q2) - self.log_alpha.detach().exp() * lp
+        target = reward + (1 - done) * self.gamma * next_q
+        for name, v in (("next_actions", na), ("next_log_prob", lp), ("next_q", torch.cat([q1, q2], dim=1)),
+                        ("heads", torch.cat([mean, raw], dim=1)), ("eps_out", eps)):
+            if outs[name] is not None:
+                outs[name].copy_(v.reshape(outs[name].shape))
+        return target
+
+    def __call__(self, rows, out=None, draw=None, eps=None, next_actions=None, next_log_prob=None, next_q=None,
+                 heads=None, eps_out=None):
+        B = int(rows.shape[0])
+        if eps is None:
+            if draw is None:
+                draw = self.draws
+                self.draws += 1
+            draw = int(draw) & (2 ** 64 - 1)
+        outs = dict(next_actions=next_actions, next_log_prob=next_log_prob, next_q=next_q, heads=heads, eps_out=eps_out)
+        if out is None:
+            out = self._out.get(B)
+            if out is None:
+                out = self._out[B] = torch.empty(B, 1, dtype=torch.float32, device=rows.device)
+        if not self.kernel:
+            A = self.actor.mean.out_features
+            e = eps if eps is not None else td_eps(self.seed & (2 ** 64 - 1), draw, B, A, rows.device)
+            out.copy_(self._torch(rows, e, outs).reshape(out.shape))
+            return out.reshape(B, 1)
+        for t in (rows, out, eps) + tuple(outs.values()):
+            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError("TdTarget: contiguous float32 tensors are required")
+        a, ak, ck = self.actor, self.ak, self.ck
+        pa, p1, p2 = self.ptrs()
+        L.check(self.lib.pd_sac_td_target(B, ak.S, ak.A, _ptr(rows), int(rows.shape[1]), ak.H, ak.nl, pa,
+                                          a.log_std_min, a.log_std_max, a.max_action, ck.H, ck.nl, p1, p2,
+                                          _ptr(self.log_alpha), self.gamma, self.seed & (2 ** 64 - 1),
+                                          0 if eps is not None else draw, _ptr(eps), _ptr(out), _ptr(next_actions),
+                                          _ptr(next_log_prob), _ptr(next_q), _ptr(heads), _ptr(eps_out),
+                                          _stream(rows.device)))
+        return out.reshape(B, 1)
 
 
 class SACCollector:
