@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PD_ABI_VERSION 11  /* 4: pd_config.integrator (was padding); 5: pd_count_work, pd_step_sac; 6: cell pieces (pd_cell_piece_info, stats word 44); 7: pd_step_sac_ring, pd_sac_actor, stats word 45; 8: pd_step_sac_fused, pd_atm_table; 9: pd_config.table_flags, pd_tuning, caller scratch for pd_pso_swarm_minima, state/action dims of pd_step_sac_fused; 10: step launches insert their own solved misses (pd_flush_misses optional), explicit list settings turn the auto refill off; 11: pd_pso_step_chunked, pd_rollout_policy_chunked; pd_rollout_sac, then pd_atm_table_lds, pd_wind_slopes and PD_TABLES_NO_ATM_LDS added later as additive exports (the version stays 11: no layout or existing call changes) */
+#define PD_ABI_VERSION 11  /* 4: pd_config.integrator (was padding); 5: pd_count_work, pd_step_sac; 6: cell pieces (pd_cell_piece_info, stats word 44); 7: pd_step_sac_ring, pd_sac_actor, stats word 45; 8: pd_step_sac_fused, pd_atm_table; 9: pd_config.table_flags, pd_tuning, caller scratch for pd_pso_swarm_minima, state/action dims of pd_step_sac_fused; 10: step launches insert their own solved misses (pd_flush_misses optional), explicit list settings turn the auto refill off; 11: pd_pso_step_chunked, pd_rollout_policy_chunked; pd_rollout_sac, then pd_atm_table_lds, pd_wind_slopes, PD_TABLES_NO_ATM_LDS and PD_TABLES_NO_PACE added later as additive exports (the version stays 11: no layout or existing call changes) */
 #define PD_MAX_PTS 256      /* aero scatter points per table */
 #define PD_MAX_COLS 5       /* AoA columns per aero table */
 #define PD_MAX_TAB 64       /* grid-fin table length */
@@ -82,7 +82,8 @@ typedef enum {
     PD_TABLES_EXACT_ATMOSPHERE = 4, /* the ISA closed form on the device, never the tabulated pieces */
     PD_TABLES_VERBOSE = 8,          /* print the table builders' statistics to stderr at create */
     PD_TABLES_NO_CARRY = 16,        /* the step kernel's searches take no carried interval as a guess */
-    PD_TABLES_NO_ATM_LDS = 32       /* no coarse atmosphere table in the 512-thread step kernels' LDS: the closed form */
+    PD_TABLES_NO_ATM_LDS = 32,      /* no coarse atmosphere table in the 512-thread step kernels' LDS: the closed form */
+    PD_TABLES_NO_PACE = 64          /* the 512-thread step kernels' waves never change their issue priority (builds with PD_PACE; the same bits either way) */
 } pd_table_flags;
 
 /* One neighbourhood-aero table: scatter points grouped by AoA column, Mach-sorted inside. */

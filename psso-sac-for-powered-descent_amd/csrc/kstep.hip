@@ -59,3 +59,13 @@ template void launch_policy_lpe<KR, PD_KPH, KW, 4>(const StepArgs<KR>&, int64_t,
 template void launch_policy_lpe<KR, PD_KPH, KW, 8>(const StepArgs<KR>&, int64_t, hipStream_t);
 #endif
 }  // namespace pd
+
+// -DPD_WAVE_TIMES (diagnostic builds of the c3 unit; tools/wave_times.py): the per-wave records of
+// the last 512-thread step launch, n waves of pd::kWaveRec words each
+#if defined(PD_WAVE_TIMES) && PD_KR == 0 && PD_KPH == 0 && PD_KW == 1 && !defined(PD_KROLL) && !defined(PD_KRK4) && \
+    !defined(PD_KLPE)
+extern "C" int pd_debug_wave_times(void* out, int n) {
+    if (n < 0 || n > pd::kWaveRecWaves) return (int)hipErrorInvalidValue;
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pd::g_wave_rec), (size_t)n * pd::kWaveRec * 8, 0, hipMemcpyDeviceToHost);
+}
+#endif

@@ -45,6 +45,17 @@ constexpr int kStepBlock = 256;
 #ifndef PD_MERGE
 #define PD_MERGE 2
 #endif
+// PD_PACE (the 512-thread kernels only, whose two waves per SIMD sit in one workgroup): pacing of a
+// SIMD's pair of waves by s_setprio, so that neither runs ahead of the other over the launch
+// ("Pacing the two waves of a SIMD, measured").  Bit 0 (value 1): at the head of
+// every env-step a wave publishes its step index in LDS, reads its partner's, and runs at priority
+// 1 while it is behind, at 0 otherwise.  Bit 1 (value 2): the same per sub-step (takes precedence
+// over bit 0).  Bit 2 (value 4, alone): no communication, the priority flips with the step's
+// parity, the two halves of the workgroup on opposite parities.  0: the kernel without any of it.
+// PD_TABLES_NO_PACE (kArgNoPace) keeps every wave at priority 0 at run time.
+#ifndef PD_PACE
+#define PD_PACE 1
+#endif
 template <typename R, int PHASE, bool WIND, int LPE, int POL, bool RK4, bool SAC> constexpr bool step_big() {
     return PD_WG512 != 0 && sizeof(R) == 8 && PHASE == 0 && WIND && LPE == 2 && POL == 0 && !RK4 && !SAC;
 }
@@ -294,7 +305,7 @@ __device__ void insert_pending(unsigned long long* count, const unsigned long lo
     *count = 0;
 }
 
-constexpr int kArgCount = 1, kArgNoCarry = 2;   // StepArgs::count_work bits
+constexpr int kArgCount = 1, kArgNoCarry = 2, kArgNoPace = 4;   // StepArgs::count_work bits
 // k_step's ROLL parameter: the actor inside the fused-step loop (SAC, 16 lanes per env) -- off, whole
 // episodes with freezing envs (pd_rollout_sac), or collection steps with auto-reset and the replay
 // ring (pd_collect_sac)
@@ -327,7 +338,8 @@ template <typename R> struct StepArgs {
     int rtd_none;                    // PD_RTD_NONE: physics stepping only (reward/done/trunc 0)
     int n_fused;                     // env-steps per launch (actions/outputs: [n_fused][N] rows)
     // bit 0 (kArgCount): workload counters on (pd_count_work; diagnostic launches); bit 1
-    // (kArgNoCarry): PD_TABLES_NO_CARRY, the searches take no carried guess
+    // (kArgNoCarry): PD_TABLES_NO_CARRY, the searches take no carried guess; bit 2 (kArgNoPace):
+    // PD_TABLES_NO_PACE, the 512-thread kernels' waves stay at priority 0
     int count_work;
     // pd_step_sac (single-step launches): the action sampled from the actor's heads in the kernel,
     // tanh(mean + exp(clamp(log_std, lo, hi)) eps) max (eps NULL: tanh(mean) max), and float32

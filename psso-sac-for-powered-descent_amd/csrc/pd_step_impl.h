@@ -5,6 +5,16 @@
 
 namespace pd {
 
+// PD_WAVE_TIMES (diagnostic builds only, like PD_STAMP; tools/wave_times.py): every wave of the
+// last launch of a 512-thread step kernel leaves kWaveRec words -- 0, 1 its start and end clock
+// (s_memrealtime, 100 MHz), 2 HW_ID, 3 XCC_ID, 4 its index in the workgroup, 5..12 its clock after
+// env-steps 16, 32, .. 128 of the launch, 13 the partner wave that the pacing found (PD_PACE bits
+// 0/1; -1 none) -- read back by pd_debug_wave_times (kstep.hip, the c3 unit)
+#ifdef PD_WAVE_TIMES
+constexpr int kWaveRec = 16, kWaveRecWaves = 16384;
+static __device__ unsigned long long g_wave_rec[kWaveRecWaves * kWaveRec];
+#endif
+
 // ---------------------------------------------------------------- lane pairs
 // Value of the partner lane (2k <-> 2k+1) by a DPP quad permutation [1,0,3,2] (no LDS
 // crossbar).  Only at converged points of the wave.
@@ -791,7 +801,8 @@ __device__ __forceinline__ R rbf_balanced(DP<R>& P, BalLds<R>& B, const R* tab, 
 // the other table hits by the balanced payload sums, misses by the cooperative solve (whose
 // evaluation, rbf_eval, has the balanced sums' bits).  Lanes with act = false (past the batch,
 // frozen policy envs) only take part.
-template <typename R, typename Pre, typename AT>
+// PACE (the 512-thread kernels with PD_PACE): the wave may be at priority 1 here
+template <typename R, bool PACE = false, typename Pre, typename AT>
 __device__ __forceinline__ R rbf2(const AT& a, DP<R>& P, int table, const TabView<R>& t, const LineLds<R>& ln,
                                   RbfCache<R>& cache, R M, R aq, bool act, BalLds<R>& B, const R* tab,
                                   WaveCount& wc, Pre&& pre, unsigned long long* stamp = nullptr) {
@@ -846,6 +857,9 @@ __device__ __forceinline__ R rbf2(const AT& a, DP<R>& P, int table, const TabVie
         wc.add_n(kStWMixed - kStWork, (__ballot(act && tr.line) != 0ull) && (__ballot(act && !tr.line) != 0ull));
     }
     if (__ballot(miss)) {
+        // a raised wave never waits on another: back to priority 0 before the miss solve's spin on
+        // its slot's lock, which the SIMD partner may hold (the next step head sets it again)
+        if constexpr (PACE) __builtin_amdgcn_s_setprio(0);
         R mv = rbf_miss_wave<R>(a, P, table, t.smach, cache.key, M, aq, 0, 1, miss);
         if (miss) val = mv;
     }
@@ -1113,6 +1127,34 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
     constexpr int EPB = kStepBlock / LPE;   // envs per workgroup
     constexpr bool kEpi = ROLL == kRollEpisodes, kCol = ROLL == kRollCollect;
     __shared__ StepLds<R, WIND, EPB, LPE == 2, CNT, kStepBlock, kBig> L;
+    // PD_PACE (pd_step.h): the 512-thread kernels only.  kPaceFb: progress feedback between the two
+    // waves of a SIMD, per env-step or (kPaceSub) per sub-step; kPaceFlip: the parity control.
+    // s_pace[w]: wave w's SIMD (HW_ID), written before the staging barrier; s_pace[8 + w]: the steps
+    // (sub-steps) it has begun, kPaceFin once it has left the step loop; s_pace[16 + w]: which
+    // progress word it reads (below); s_pace[24 + w]: its partner, for PD_WAVE_TIMES.  Volatile
+    // accesses, no barrier: a stale value only delays a decision by a step.
+    // A raised wave never waits on another wave: the priority is dropped to 0 before the miss
+    // solve's lock (rbf2), and on leaving the step loop, ahead of the end-of-launch barrier and
+    // ticket; those and the staging barrier (before any raise) are the kernel's only waits between
+    // waves (the SAC and ROLL barriers are not in these instantiations).
+    constexpr int kPaceBits = kBig ? (PD_PACE) : 0;
+    constexpr bool kPaceSub = (kPaceBits & 2) != 0, kPaceFb = (kPaceBits & 3) != 0;
+    constexpr bool kPaceFlip = !kPaceFb && (kPaceBits & 4) != 0;
+    constexpr unsigned kPaceFin = 0xffffffffu;
+    __shared__ unsigned s_pace[kPaceFb ? 32 : 1];
+    // (an LDS-address-space pointer: volatile accesses through a generic one stay flat loads)
+    using PaceWord = volatile __attribute__((address_space(3))) unsigned;
+    if constexpr (kPaceFb) {
+        unsigned hw;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        // (every lane stores the wave's value: a branch for one lane here, at the head of the block
+        // that requests the env's state and the tables, made the register allocator spill)
+        ((PaceWord*)s_pace)[threadIdx.x >> 6] = (hw >> 4) & 3u;
+        ((PaceWord*)s_pace)[8 + (threadIdx.x >> 6)] = 0u;
+    }
+#ifdef PD_WAVE_TIMES
+    const unsigned long long wt0_ = __builtin_amdgcn_s_memrealtime();
+#endif
 #ifdef PD_STAMP
     unsigned long long acc_[17] = {};   // [7], [8]: rbf2 lookup, evaluation; [9..12] lookup parts; [13..16] post-aero parts
 #endif
@@ -1272,6 +1314,31 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
         if (threadIdx.x < 2) L.tdesc[threadIdx.x] = tab_view<R>(P, L.tab, (int)threadIdx.x);
     }
     __syncthreads();
+    // the wave's partner: the one other wave of the workgroup on its SIMD (not assumed to be wave
+    // w + 4); a wave with none or with several does not pace.
+    // s_pace[16 + w]: the progress word wave w compares its own with -- its partner's, or its own
+    // (never behind: priority 0) without a partner or under PD_TABLES_NO_PACE.  Kept in LDS, written
+    // and read by wave w alone: the sub-step loop has no scalar register to spare for it
+    if constexpr (kPaceFb) {
+        const int wv = (int)(threadIdx.x >> 6);
+        constexpr int kWv = kStepBlock / 64;
+        PaceWord* sp = (PaceWord*)s_pace;
+        const unsigned mine = sp[wv];
+        int cnt = 0, peer = -1;
+#pragma unroll
+        for (int k = 0; k < kWv; ++k) {
+            const bool same = k != wv && sp[k] == mine;
+            cnt += same ? 1 : 0;
+            peer = same ? k : peer;
+        }
+        const bool paced = cnt == 1 && !(a.count_work & kArgNoPace);
+        sp[16 + wv] = 8u + (unsigned)(paced ? peer : wv);
+#ifdef PD_WAVE_TIMES
+        sp[24 + wv] = (unsigned)(paced ? peer : -1);
+#endif
+    }
+    bool pace_flip = false;   // (kPaceFlip: paced at all)
+    if constexpr (kPaceFlip) pace_flip = !(a.count_work & kArgNoPace);
     PD_T(t_staged);
     PD_ACC(0, t_staged - t_start);
     if constexpr (POL) {
@@ -1442,9 +1509,44 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
         for (int k = 0; k < A; ++k) { an0[k] = 0u; an1[k] = 0u; }
         if (nf > 0) act_request(0);
     }
+    // PD_PACE feedback: publish the count of steps (sub-steps) begun, read the partner's, and run
+    // at priority 1 while behind it, at 0 otherwise or once it has finished.  The condition is in a
+    // scalar register (readfirstlane): a scalar branch around each s_setprio
+    auto pace = [&](unsigned begun) {
+        if constexpr (kPaceFb) {
+            PaceWord* sp = (PaceWord*)s_pace;
+            const unsigned wv = threadIdx.x >> 6;
+            const unsigned peer = sp[16 + wv] & 15u;   // (8..15: the index stays inside s_pace whatever is read)
+            sp[8 + wv] = begun;
+            const unsigned pf = (unsigned)__builtin_amdgcn_readfirstlane((int)sp[peer]);
+            if (pf != kPaceFin && pf > begun) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+        }
+    };
+#ifdef PD_WAVE_TIMES
+    const unsigned wt_wid_ = blockIdx.x * (kStepBlock / 64) + (threadIdx.x >> 6);
+    auto wt_sample = [&](int done) {   // after `done` env-steps, a multiple of 16
+        if constexpr (kBig) {
+            if (done && !(done & 15) && done <= 128 && __lane_id() == 0 && wt_wid_ < (unsigned)kWaveRecWaves)
+                g_wave_rec[(size_t)wt_wid_ * kWaveRec + 4 + (done >> 4)] = __builtin_amdgcn_s_memrealtime();
+        }
+    };
+#endif
 #pragma unroll 1
     for (int f = 0; f < nf; ++f) {
     SA<R>& a = kargs<R>();
+#ifdef PD_WAVE_TIMES
+    wt_sample(f);
+#endif
+    if constexpr (kPaceFb && !kPaceSub) pace((unsigned)f + 1u);
+    if constexpr (kPaceFlip) {
+        // the control without communication: the priority by the step's parity, the workgroup's
+        // waves 0-3 and 4-7 on opposite parities
+        if (pace_flip) {
+            if (__builtin_amdgcn_readfirstlane((f ^ (int)(threadIdx.x >> 8)) & 1)) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+        }
+    }
     const size_t fo = (size_t)f * (size_t)N;
     float uf[A];
     double ud[A];
@@ -1604,6 +1706,7 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
         SA<R>& a = kargs<R>();
         DP<R>& P = *params<R>(a.P);
         const bool tap_sub = tap && sub == NSUB - 1;
+        if constexpr (kPaceSub) pace((unsigned)(NSUB * f + sub) + 1u);
         // PD_TABLES_NO_CARRY: every guess fails
         if constexpr (kCarry) { if (a.count_work & kArgNoCarry) carry = kCarryNone; }
         RS x = SV(0), y = SV(1), vx = SV(2), vy = SV(3), th = SV(4), thd = SV(5), ga = SV(6), al = SV(7);
@@ -1723,7 +1826,7 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
             } else {
                 R v;
                 if constexpr (LPE == 2)
-                    v = rbf2<R>(a, P, my_table, tab_view_lds<R>(L.tdesc, my_table), L.lines, cA, mach,
+                    v = rbf2<R, (kPaceFb || kPaceFlip)>(a, P, my_table, tab_view_lds<R>(L.tdesc, my_table), L.lines, cA, mach,
                                 my_table ? aq_cl : aq_cd, live, L.bal[threadIdx.x >> 6], L.tab, wc, wind_block
 #ifdef PD_STAMP
                                 , acc_ + 7
@@ -2385,6 +2488,15 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
     }
     }   // (ROLL: the wave's step)
     }   // fused steps
+    if constexpr (kPaceFb || kPaceFlip) {
+        // out of the step loop: "finished" for the partner, and priority 0 ahead of the
+        // end-of-launch barrier and ticket
+        if constexpr (kPaceFb) ((PaceWord*)s_pace)[8 + (threadIdx.x >> 6)] = kPaceFin;
+        __builtin_amdgcn_s_setprio(0);
+    }
+#ifdef PD_WAVE_TIMES
+    wt_sample(nf);
+#endif
     if constexpr (POL) {
         // done-mask compaction: the envs whose episode goes on, in lane order, appended to the
         // next launch's list at a base taken by one atomic per wave (the count also tells the
@@ -2407,6 +2519,22 @@ __attribute__((amdgpu_waves_per_eu(2))) void k_step(StepArgs<R> a_) {
     // with no live env -- and goes on in the rollout's next launch, or the caller's next call)
     if constexpr (kEpi) { if (live) roll_store(a.roll_t0 + nf, 0, e.tid, false); }
     store_all();
+#ifdef PD_WAVE_TIMES
+    if constexpr (kBig) {
+        __builtin_amdgcn_s_waitcnt(0);
+        const unsigned long long wt1_ = __builtin_amdgcn_s_memrealtime();
+        unsigned hw, xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        if (__lane_id() == 0 && wt_wid_ < (unsigned)kWaveRecWaves) {
+            unsigned long long* rec = g_wave_rec + (size_t)wt_wid_ * kWaveRec;
+            rec[0] = wt0_; rec[1] = wt1_; rec[2] = hw; rec[3] = xcc; rec[4] = threadIdx.x >> 6;
+            long long peer = -1;
+            if constexpr (kPaceFb) peer = (long long)(int)((PaceWord*)s_pace)[24 + (threadIdx.x >> 6)];
+            rec[13] = (unsigned long long)peer;
+        }
+    }
+#endif
     if constexpr (SAC) {
         // ring mode: the launch's last workgroup (a ticket per workgroup, taken after all of its
         // ring rows are written and its position read) advances the ring's position and size

@@ -231,7 +231,8 @@ template <typename R> StepArgs<R> make_args(pd_env* e) {
     a.dt_aux = e->cfg.dt > 0.0 ? e->cfg.dt : 0.1;
     a.rtd_none = e->cfg.rtd == PD_RTD_NONE;
     a.n_fused = 1;
-    a.count_work = (e->count_work ? kArgCount : 0) | ((e->cfg.table_flags & PD_TABLES_NO_CARRY) ? kArgNoCarry : 0);
+    a.count_work = (e->count_work ? kArgCount : 0) | ((e->cfg.table_flags & PD_TABLES_NO_CARRY) ? kArgNoCarry : 0) |
+                   ((e->cfg.table_flags & PD_TABLES_NO_PACE) ? kArgNoPace : 0);
     return a;
 }
 
@@ -271,7 +272,7 @@ pd_status validate(const pd_params* p, const pd_config* c) {
     if (c->precision != PD_F64 && c->precision != PD_F32) return fail(PD_ERR_INVALID, "bad precision");
     if (c->integrator != PD_INTEG_REFERENCE && c->integrator != PD_INTEG_RK4) return fail(PD_ERR_INVALID, "bad integrator");
     if (c->table_flags & ~(PD_TABLES_NO_CELL_PIECES | PD_TABLES_NO_FINE_INDEX | PD_TABLES_EXACT_ATMOSPHERE | PD_TABLES_VERBOSE |
-                           PD_TABLES_NO_CARRY | PD_TABLES_NO_ATM_LDS))
+                           PD_TABLES_NO_CARRY | PD_TABLES_NO_ATM_LDS | PD_TABLES_NO_PACE))
         return fail(PD_ERR_INVALID, "unknown table_flags bits");
     if (c->integrator == PD_INTEG_RK4 && (c->phase != PD_PHASE_PURE_THROTTLE || c->enable_wind))
         return fail(PD_ERR_UNSUPPORTED, "the RK4 integrator (non-parity, BASELINE c2) exists for "

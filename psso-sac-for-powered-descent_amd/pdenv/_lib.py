@@ -84,6 +84,7 @@ class PdConfig(C.Structure):
 # pd_table_flags
 TABLES_NO_CELL_PIECES, TABLES_NO_FINE_INDEX, TABLES_EXACT_ATMOSPHERE, TABLES_VERBOSE, TABLES_NO_CARRY = 1, 2, 4, 8, 16
 TABLES_NO_ATM_LDS = 32
+TABLES_NO_PACE = 64
 
 
 class PdTuning(C.Structure):
