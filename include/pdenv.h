@@ -571,6 +571,70 @@ pd_status pd_sac_td_target(int64_t batch, int32_t state_dim, int32_t action_dim,
                            const float* log_alpha, float gamma, uint64_t seed, uint64_t draw, const float* eps_in,
                            float* target_q, float* next_actions, float* next_log_prob, float* next_q, float* heads,
                            float* eps_out, void* stream);
+/* The critic step of SACPyTorch.update on the device (csrc/pdsacupd.hip), in three launches and
+ * without a host synchronisation: pd_sac_critic_grad (two launches) replaces sac_pytorch.py:445-471
+ * -- critic(states, actions), the four losses of :457-468, critic_optimizer.zero_grad() and
+ * critic_loss.backward() -- and the |td| of :526; pd_adam_step (one launch) replaces :474-483 and
+ * :530-531 -- clip_grad_norm_, critic_optimizer.step() and the Polyak loop.  All float32; no float
+ * atomics: every sum has a fixed order, so the same inputs give the same bits on every call.
+ *
+ * Scratch of pd_sac_critic_grad: with Bp = 16 ceil(batch / 16), the post-ReLU activations and the
+ * deltas of every layer of both nets [2][L][Bp][H] each, the two nets' dq and |target - q| [2][Bp]
+ * each and the row tiles' loss partials [Bp / 16][2]:
+ *   bytes = 4 (4 L H Bp + 4 Bp + Bp / 8)
+ * (0 for a batch, hidden or n_hidden_layers below 1).  Owned by the caller, 16-byte aligned; calls
+ * that may overlap need their own. */
+#define PD_SAC_LOSS_L2 0   /* F.mse_loss: per-row dq = 2 w (q - target) / B */
+#define PD_SAC_LOSS_L1 1   /* F.l1_loss:  per-row dq = w sign(q - target) / B, sign(0) = 0 */
+#define PD_ADAM_MAX_TENSORS 64
+size_t pd_sac_critic_grad_scratch_bytes(int64_t batch, int32_t hidden, int32_t n_hidden_layers);
+/* q = critic(state | action), the loss and its gradient with respect to every parameter of both
+ * Q nets.  sa: state | action are the first state_dim + action_dim floats of each of `batch` rows
+ * `pitch` floats apart (pitch = the row width W for a buffer's last_rows, state_dim + action_dim for
+ * a packed tensor).  target_q [batch]; weights [batch], the PER importance weights, or NULL (w = 1);
+ * loss_kind PD_SAC_LOSS_L2 / _L1: with the weights or without, the four losses of
+ * sac_pytorch.py:457-468.  dq_in [batch][2] or NULL: given, it is the upstream gradient dLoss/dq of
+ * (row, net) in place of the loss's own (target_q may then be NULL when neither td_abs nor loss_out
+ * is asked for).  params_q1 / params_q2 as pd_sac_critic's; grads_q1 / grads_q2: the gradient
+ * tensors (p.grad) in the same order, OVERWRITTEN, never accumulated into (zero_grad() + backward()).
+ * Outputs, each may be NULL: q [batch][2] (pd_sac_critic's bits), td_abs [batch] = max(|target - q1|,
+ * |target - q2|), dq_out [batch][2], loss_out [1] (the mean over the batch: (w l1 + w l2).mean() with
+ * weights, mean(l1) + mean(l2) without; the loss_kind's loss also under dq_in), sumsq_partials: one
+ * sum of squares of gradient elements per workgroup of the second launch, 2 (H / 64 + (L - 1) (H / 16)
+ * (H / 128) + H / 128) of them -- *n_partials holds the array's length on entry (PD_ERR_INVALID if
+ * too short) and that count on return (0 for an empty batch); their sum in index order is the
+ * squared norm pd_adam_step clips by.
+ * Domain: pd_sac_critic's (state_dim + action_dim <= 16, hidden 128 / 256 / 512, 1 to 8 hidden
+ * layers, parameters and gradients 16-byte aligned).  PD_ERR_INVALID: a negative batch, a dimension
+ * out of range, pitch below state_dim + action_dim, an unknown loss kind, a null required pointer,
+ * scratch missing, misaligned or short; PD_ERR_UNSUPPORTED: another hidden width, a misaligned
+ * parameter or gradient; all before any launch.  batch == 0: PD_OK, nothing launched. */
+pd_status pd_sac_critic_grad(int64_t batch, int32_t state_dim, int32_t action_dim, int32_t hidden,
+                             int32_t n_hidden_layers, const float* sa, int32_t pitch, const float* target_q,
+                             const float* weights, int32_t loss_kind, const float* dq_in,
+                             const float* const* params_q1, const float* const* params_q2, float* const* grads_q1,
+                             float* const* grads_q2, float* q, float* td_abs, float* dq_out, float* loss_out,
+                             float* sumsq_partials, int32_t* n_partials, void* scratch, size_t scratch_bytes,
+                             void* stream);
+/* clip_grad_norm_ (sac_pytorch.py:474-479), torch.optim.Adam.step (:483; no weight decay, no
+ * amsgrad) and the Polyak loop (:530-531) over a list of n_tensors <= PD_ADAM_MAX_TENSORS float32
+ * tensors in one launch (the host arrays are read during the call; numel[k] elements each, any
+ * alignment, a tensor of 0 elements is skipped).
+ *   max_norm > 0: total = sqrt(sum of sumsq_partials[0 .. n_partials) in index order), coef = min(1,
+ *                 max_norm / (total + 1e-6)), grads *= coef in place, grad_norm_out[0] = total (may
+ *                 be NULL); max_norm <= 0: no clipping, the gradients and grad_norm_out untouched;
+ *   Adam:         m = m + fl(1 - beta1) (g - m); v = beta2 v + (fl(1 - beta2) g) g;
+ *                 p = p - step_size (m / (sqrt(v) / bc2_sqrt + eps)), with step_size = lr / (1 -
+ *                 beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) computed by the caller in binary64 from
+ *                 the step count t (after its increment) and rounded to float32 here;
+ *   targets:      NULL, or n_tensors target tensors: t = fl(1 - tau) t + fl(tau) p on the new p, two
+ *                 rounded products and their rounded sum (torch's (1 - tau) * t + tau * p).
+ * PD_ERR_INVALID: n_tensors out of range, a null list or tensor, a negative numel, clipping
+ * without partials; before any launch. */
+pd_status pd_adam_step(int32_t n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
+                       float* const* exp_avg_sq, const int64_t* numel, float* const* targets, double step_size,
+                       double bc2_sqrt, double beta1, double beta2, double eps, double max_norm,
+                       const float* sumsq_partials, int32_t n_partials, float* grad_norm_out, double tau, void* stream);
 /* Insert the aero neighbourhoods solved on device and still queued into the handle's tables
  * (one tiny kernel; a no-op when nothing is queued).  Since ABI 10 every step launch (pd_step,
  * pd_step_n, pd_step_sac*, pd_rollout) inserts the neighbourhoods it solved itself, by its last

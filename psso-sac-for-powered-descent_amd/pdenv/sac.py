@@ -561,6 +561,232 @@ class TdTarget:
         return out.reshape(B, 1)
 
 
+class CriticUpdate:
+    """The critic step of SACPyTorch.update as three launches and no host synchronisation
+    (csrc/pdsacupd.hip): critic(states, actions), the loss of sac_pytorch.py:457-468 (MSE or L1, with
+    or without PER weights), zero_grad() + backward() (pd_sac_critic_grad: the gradients land in
+    p.grad, overwritten), then clip_grad_norm_, critic_optimizer.step() and the Polyak loop of step
+    8 (pd_adam_step), and the |td| of step 7 that buffer.update_priorities takes.
+
+    optimizer: the caller's torch.optim.Adam over critic.parameters().  Its state -- exp_avg,
+    exp_avg_sq, step -- is created if empty and then used in place, so optimizer.state_dict() and
+    load_state_dict() keep working and torch's own step() may continue from it; lr, betas and eps are
+    read from param_groups at each call; `step` (a host tensor) is advanced on the host.
+
+    td_abs = upd(rows, target_q, weights=None): rows [B, >= S + A] float32 with unit column stride
+    (state | action first: buffer.last_rows, or a packed [B, S + A]), target_q [B] or [B, 1] (TdTarget's
+    output), weights [B] or [B, 1] or None.  Returns td_abs [B]; upd.q [B, 2], upd.critic_loss [1] and
+    upd.grad_norm [1] (None without max_grad_norm) are device tensors -- reading them is the caller's
+    synchronisation.  All four are owned by the object per batch size and overwritten by the next call.
+    upd.backward(rows, target_q, weights=None, dq=None) runs the forward and backward passes only
+    (for another optimizer); dq [B, 2] replaces the loss's own gradient dLoss/dq.
+
+    Where supported() is false -- a net outside the kernels' shapes, or an optimizer that is not a
+    plain Adam (weight decay, amsgrad, maximize, capturable / fused, several param groups) -- the same
+    steps run in torch (autograd, clip_grad_norm_, optimizer.step(), the Polyak
+    loop) and return the same things."""
+
+    def __init__(self, critic, critic_target, optimizer, tau=0.005, use_l1_loss=False, max_grad_norm=None):
+        self.critic, self.critic_target, self.optimizer = critic, critic_target, optimizer
+        self.tau, self.use_l1_loss = float(tau), bool(use_l1_loss)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.kernel = self.supported(critic, optimizer, critic_target)
+        self.q = self.critic_loss = self.grad_norm = None
+        self._out = {}
+        hidden = _q_linears(critic.q1)[0]
+        self.D = hidden[0].in_features
+        if self.kernel:
+            self.lib = L.load()
+            self.ck, self.tk = CriticKernel(critic), CriticKernel(critic_target)
+            self.params = self.ck.params[0] + self.ck.params[1]
+            self.targets = self.tk.params[0] + self.tk.params[1]
+            n, vp = len(self.params), C.c_void_p
+            half = n // 2
+            self._g = ((vp * half)(), (vp * half)())
+            self._lists = tuple((vp * n)() for _ in range(5))      # params, grads, exp_avg, exp_avg_sq, targets
+            self._numel = (C.c_int64 * n)(*[p.numel() for p in self.params])
+            H, nl = self.ck.H, self.ck.nl
+            self.n_partials = 2 * (H // 64 + (nl - 1) * (H // 16) * (H // 128) + H // 128)
+            self._np = C.c_int32(0)
+
+    @staticmethod
+    def reasons(critic, optimizer, critic_target=None):
+        """Why the kernel path does not take this critic and optimizer: a list of words, empty when
+        supported -- "shape" (not two Linear-ReLU stacks of equal shape with hidden 128 / 256 / 512,
+        <= 8 hidden layers and S + A <= 16), "tensors" (parameters not contiguous float32 on the
+        device, 16-byte aligned), "target" (critic_target of other shapes), and the optimizer's:
+        "adam", "param_groups", "params", "weight_decay", "amsgrad", "maximize", "capturable", "fused",
+        "differentiable", "lr"."""
+        why = []
+        nets = [getattr(critic, "q1", None), getattr(critic, "q2", None)]
+        shapes = []
+        for net in nets:
+            hidden, last, ok = _q_linears(net) if isinstance(net, nn.Sequential) else ([], None, False)
+            if not ok or len(hidden) > 8:
+                shapes.append(None)
+                continue
+            H = hidden[0].out_features
+            good = (H in (128, 256, 512) and 2 <= hidden[0].in_features <= 16 and last.out_features == 1
+                    and last.in_features == H and all(m.in_features == H and m.out_features == H for m in hidden[1:]))
+            shapes.append((hidden[0].in_features, H, len(hidden)) if good else None)
+        if None in shapes or shapes[0] != shapes[1]:
+            why.append("shape")
+        params = list(critic.parameters())
+        if not all(p.dtype == torch.float32 and p.is_cuda and p.is_contiguous() and p.data_ptr() % 16 == 0
+                   for p in params):
+            why.append("tensors")
+        if critic_target is not None:
+            tp = list(critic_target.parameters())
+            if ([tuple(p.shape) for p in tp] != [tuple(p.shape) for p in params]
+                    or [n for n, _ in critic_target.named_parameters()] != [n for n, _ in critic.named_parameters()]):
+                why.append("target")
+            elif "tensors" not in why and not CriticKernel.supported(critic_target):
+                why.append("target")
+        if type(optimizer) is not torch.optim.Adam:
+            return why + ["adam"]
+        if len(optimizer.param_groups) != 1:
+            return why + ["param_groups"]
+        g = optimizer.param_groups[0]
+        if len(params) > L.ADAM_MAX_TENSORS or len(g["params"]) != len(params) or not all(
+                a is b for a, b in zip(g["params"], params)):
+            why.append("params")
+        if g.get("weight_decay", 0) != 0:
+            why.append("weight_decay")
+        why += [k for k in ("amsgrad", "maximize", "capturable", "fused", "differentiable") if g.get(k)]
+        if isinstance(g["lr"], torch.Tensor):
+            why.append("lr")
+        return why
+
+    @staticmethod
+    def supported(critic, optimizer, critic_target=None):
+        return not CriticUpdate.reasons(critic, optimizer, critic_target)
+
+    # ---- the torch path
+    def _loss(self, q1, q2, t, w):
+        f = F.l1_loss if self.use_l1_loss else F.mse_loss
+        if w is not None:
+            return (w * f(q1, t, reduction="none") + w * f(q2, t, reduction="none")).mean()
+        return f(q1, t) + f(q2, t)
+
+    def _torch_backward(self, rows, target_q, weights, dq):
+        B = int(rows.shape[0])
+        sa = rows[:, :self.D]
+        q1, q2 = self.critic.q1(sa), self.critic.q2(sa)
+        t = None if target_q is None else target_q.detach().reshape(B, 1)
+        w = None if weights is None else weights.detach().reshape(B, 1)
+        self.optimizer.zero_grad()
+        loss = None if t is None else self._loss(q1, q2, t, w)
+        if dq is not None:
+            torch.autograd.backward([q1, q2], [dq[:, :1], dq[:, 1:]])
+        else:
+            loss.backward()
+        self.q = torch.cat([q1, q2], dim=1).detach()
+        self.critic_loss = None if loss is None else loss.detach().reshape(1)
+        if t is None:
+            return None
+        return torch.max((t - q1).abs(), (t - q2).abs()).detach().reshape(B)
+
+    def _torch_step(self):
+        self.grad_norm = None
+        if self.max_grad_norm is not None:
+            self.grad_norm = torch.nn.utils.clip_grad_norm_(self.critic.parameters(),
+                                                            max_norm=self.max_grad_norm).reshape(1)
+        self.optimizer.step()
+        with torch.no_grad():
+            for p, tp in zip(self.critic.parameters(), self.critic_target.parameters()):
+                tp.data.copy_((1 - self.tau) * tp.data + self.tau * p.data)
+
+    # ---- the kernel path
+    def _buffers(self, B, dev):
+        out = self._out.get(B)
+        if out is None:
+            nbytes = int(self.lib.pd_sac_critic_grad_scratch_bytes(B, self.ck.H, self.ck.nl))
+            f32 = dict(dtype=torch.float32, device=dev)
+            out = dict(q=torch.empty(B, 2, **f32), td_abs=torch.empty(B, **f32), loss=torch.empty(1, **f32),
+                       grad_norm=torch.empty(1, **f32), partials=torch.empty(self.n_partials, **f32),
+                       scratch=torch.empty((nbytes + 3) // 4, **f32))
+            self._out[B] = out
+        return out
+
+    def _grad_ptrs(self):
+        half = len(self.params) // 2
+        for k, p in enumerate(self.params):
+            if p.grad is None or not (p.grad.is_contiguous() and p.grad.dtype == torch.float32):
+                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            self._g[k // half][k % half] = p.grad.data_ptr()
+        return self._g
+
+    def _kernel_backward(self, rows, target_q, weights, dq):
+        B = int(rows.shape[0])
+        for t in (target_q, weights, dq):
+            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() in (B, 2 * B)):
+                raise ValueError("CriticUpdate: contiguous float32 tensors of the batch's length are required")
+        if not (rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[1] >= self.D
+                and (B == 0 or rows.stride(1) == 1)):
+            raise ValueError("CriticUpdate: rows [B, >= S + A] float32 with unit column stride are required")
+        o = self._buffers(B, rows.device)
+        p1, p2 = self.ck.ptrs()
+        g1, g2 = self._grad_ptrs()
+        self._np.value = self.n_partials
+        want = target_q is not None
+        L.check(self.lib.pd_sac_critic_grad(B, self.D - 1, 1, self.ck.H, self.ck.nl, _ptr(rows),
+                                            int(rows.stride(0)) if B else self.D, _ptr(target_q), _ptr(weights),
+                                            L.SAC_LOSS_L1 if self.use_l1_loss else L.SAC_LOSS_L2, _ptr(dq), p1, p2, g1, g2,
+                                            _ptr(o["q"]), _ptr(o["td_abs"]) if want else None, None,
+                                            _ptr(o["loss"]) if want else None, _ptr(o["partials"]), C.byref(self._np),
+                                            _ptr(o["scratch"]), o["scratch"].numel() * 4, _stream(rows.device)))
+        self.q, self.critic_loss = o["q"], (o["loss"] if want else None)
+        return o["td_abs"] if want else None
+
+    def _ensure_state(self):
+        st = self.optimizer.state
+        for p in self.params:
+            s = st[p]
+            if len(s) == 0:
+                s["step"] = torch.tensor(0.0, dtype=torch.float32)
+                s["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                s["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            elif s["step"].is_cuda:
+                s["step"] = s["step"].cpu()
+
+    def _kernel_step(self, B, dev):
+        self._ensure_state()
+        st, g = self.optimizer.state, self.optimizer.param_groups[0]
+        lp, lg, lm, lv, lt = self._lists
+        for k, (p, tp) in enumerate(zip(self.params, self.targets)):
+            s = st[p]
+            s["step"] += 1                                   # (a host tensor: no device work)
+            lp[k], lg[k], lt[k] = p.data_ptr(), p.grad.data_ptr(), tp.data_ptr()
+            lm[k], lv[k] = s["exp_avg"].data_ptr(), s["exp_avg_sq"].data_ptr()
+        t = int(st[self.params[0]]["step"].item())
+        beta1, beta2 = g["betas"]
+        bc1, bc2 = 1 - beta1 ** t, 1 - beta2 ** t
+        o = self._buffers(B, dev)
+        clip = self.max_grad_norm is not None
+        L.check(self.lib.pd_adam_step(len(self.params), lp, lg, lm, lv, self._numel, lt, float(g["lr"]) / bc1,
+                                      bc2 ** 0.5, beta1, beta2, float(g["eps"]),
+                                      self.max_grad_norm if clip else 0.0, _ptr(o["partials"]), self.n_partials,
+                                      _ptr(o["grad_norm"]), self.tau, _stream(dev)))
+        self.grad_norm = o["grad_norm"] if clip else None
+
+    def backward(self, rows, target_q, weights=None, dq=None):
+        """The forward and backward passes alone: the gradients in p.grad (overwritten), q and
+        critic_loss set; returns td_abs [B] (None without target_q)."""
+        if not self.kernel:
+            return self._torch_backward(rows, target_q, weights, dq)
+        return self._kernel_backward(rows, target_q, weights, dq)
+
+    def __call__(self, rows, target_q, weights=None):
+        td_abs = self.backward(rows, target_q, weights)
+        if int(rows.shape[0]) == 0:
+            return td_abs
+        if self.kernel:
+            self._kernel_step(int(rows.shape[0]), rows.device)
+        else:
+            self._torch_step()
+        return td_abs
+
+
 class SACCollector:
     """One collection step of N envs on this rank: actor -> env step -> transition rows -> (gather)
     -> learner-rank buffer.  `obs` always holds the observation the actor sees next (the
