@@ -635,6 +635,85 @@ pd_status pd_adam_step(int32_t n_tensors, float* const* params, float* const* gr
                        float* const* exp_avg_sq, const int64_t* numel, float* const* targets, double step_size,
                        double bc2_sqrt, double beta1, double beta2, double eps, double max_norm,
                        const float* sumsq_partials, int32_t n_partials, float* grad_norm_out, double tau, void* stream);
+/* The gradient of each Q net of the twin critic with respect to its input, with unit upstream
+ * gradient (the actor step's way through the critic, sac_pytorch.py:487-497), in one launch over
+ * batch rows of state | action (the first state_dim + action_dim floats of a row, rows pitch floats
+ * apart, as pd_sac_critic_grad takes them).  Outputs, each may be NULL: q [batch][2] (pd_sac_critic's
+ * bits) and dsa [batch][2][state_dim + action_dim], dsa[b][k][c] = d q_k / d input_c.
+ * Order of operations (float32): the forward pass is pd_sac_critic's; delta_{L-1}[j] = wm[j] (h_{L-1}[j]
+ * > 0); delta_{l-1} = (delta_l . W_l) (h_{l-1} > 0) as pd_sac_critic_grad's chain (k ascending over W_l's
+ * rows, one rounding per fma step); dsa[c] = sum_j delta_0[j] W1[j][c] in 16 parts of H / 16 consecutive
+ * j, fma in ascending j within a part from 0, the parts joined by the head stage's tree (p ^ 8, ^ 4, ^ 2,
+ * ^ 1).  On integer nets every step is exact.  No deltas are stored and no scratch is needed: the layers'
+ * signs are kept in LDS.  Domain and refusals: pd_sac_critic's, and PD_ERR_INVALID for a pitch below
+ * state_dim + action_dim; all before any launch.  batch == 0: PD_OK, nothing launched. */
+pd_status pd_sac_critic_dinput(int64_t batch, int32_t state_dim, int32_t action_dim, int32_t hidden,
+                               int32_t n_hidden_layers, const float* sa, int32_t pitch, const float* const* params_q1,
+                               const float* const* params_q2, float* q, float* dsa, void* stream);
+/* Bytes of scratch pd_sac_actor_grad needs: 4 (Bp (2 L H + 5 A + 19) + Bp / 8) with Bp = 16 ceil(batch /
+ * 16), H = actor_hidden, L = actor_layers, A = action_dim (the actor's post-ReLU tiles and deltas, and
+ * per row the head gradients padded to 16, heads, eps, dq/da, q, log_prob; two loss partials a row tile;
+ * the critic needs none).  0 for a non-positive argument. */
+size_t pd_sac_actor_grad_scratch_bytes(int64_t batch, int32_t action_dim, int32_t actor_hidden, int32_t actor_layers);
+/* The actor and temperature steps of SACPyTorch.update up to the optimizers (sac_pytorch.py:485-497 and
+ * :512-520): actor.sample(states), critic(states, new_actions) with the CURRENT critic, min(q1, q2), the
+ * actor loss with PER weights (weights [batch]) or without (NULL), zero_grad() + backward() through both
+ * Q nets into the actor, and the temperature loss and its gradient; three launches, no host
+ * synchronisation, no atomics.  The optimizer steps are pd_adam_step's: one call over the actor's
+ * tensors with sumsq_partials for the clip, one over the one-element log_alpha with log_alpha_grad.
+ * rows: batch rows, pitch floats apart, whose first state_dim floats are the state (a replay sample's
+ * [B][2S + A + 2] rows, or packed states).  actor_params / actor_grads: pd_sac_actor's order (w, b of
+ * each hidden layer, mean.weight, mean.bias, log_std.weight, log_std.bias); the gradients are
+ * overwritten, never accumulated.  log_alpha: a device float32 scalar, read once (alpha =
+ * expf(*log_alpha)); no launch of this call writes it.  eps_in [batch][A] or NULL: drawn, Philox4x32-10
+ * with key (lo32(seed), hi32(seed)) and counter (row, lo32(draw), hi32(draw), 72 + k / 2), Box-Muller as
+ * pd_sac_td_target -- the tag differs (64 there), so the same (seed, draw) gives noise independent of the
+ * TD target's.  dheads_in [batch][2A] or NULL: given, it replaces dLoss / d(mean | raw log_std); the
+ * critic pointers may then be NULL and q, dq_da and actor_loss are not written.
+ * Per row b and component k, float32 in this order (w = weights[b] or 1, Bf = (float)batch):
+ *   heads            Actor.forward(state), unclamped: pd_sac_actor's bits
+ *   sample           raw = log_std head; ls = clamp(raw, lo, hi); sd = expf(ls); x = m + sd eps; a =
+ *                    tanhf(x); new_action = a max_action; log_prob = sum_k (-(d d) / (2 (sd sd)) - ls -
+ *                    0.9189385332046727 - logf(1 - a a + 1e-6)), d = x - m, k ascending: pd_sac_td_target's
+ *                    bits for the same state and eps
+ *   q_j              Q_j(state | new_action), j = 1, 2: pd_sac_critic's bits
+ *   dq_da[j][k]      pd_sac_critic_dinput's action columns
+ *   coefficients     sel_j = 1 for the smaller q, 0 for the larger, 1/2 each on a tie (torch.min's
+ *                    backward); c_j = -((w / Bf) sel_j); cl = (w alpha) / Bf
+ *   sample backward  t = 1 - a a; G = c_1 dq_da[1][k] + c_2 dq_da[2][k]; gx = (G max_action) t + cl (((2 a) t)
+ *                    / (t + 1e-6)); dmean = gx; draw = ((gx sd) eps - cl) if lo <= raw <= hi (torch.clamp
+ *                    passes the gradient at both bounds), else 0.  The two paths of Normal.log_prob's
+ *                    quadratic term, through x and through mean / std, cancel analytically ((x - m) / sd is
+ *                    eps) and are left out; float32 autograd keeps their rounding residue.
+ *   actor backward   delta_{L-1}[j] = (fma chain from 0 over dmean_k Wm[k][j], k ascending, then draw_k
+ *                    Ws[k][j], k ascending) (h_{L-1}[j] > 0); the hidden chain as pd_sac_critic_grad's; dW_l
+ *                    = delta_l^T h_{l-1} with the batch rows added in ascending order, four an MFMA
+ *                    instruction; [dWm ; dWs] one row tile of 2A rows; the biases the column sums.
+ *   losses           per row la = w (alpha log_prob - fminf(q1, q2)), lt = w (log_prob + target_entropy);
+ *                    the 16 rows of a tile added in ascending order, the tiles in ascending order;
+ *                    actor_loss = S_la / Bf; log_alpha_grad = -(S_lt / Bf); alpha_loss = log_alpha
+ *                    log_alpha_grad (sac_pytorch.py:515-517).
+ * Outputs, each may be NULL: new_actions [B][A], log_prob [B], q [B][2], heads [B][2A], eps_out [B][A],
+ * dq_da [B][2][A], dheads_out [B][2A] (dmean | draw), actor_loss [1], alpha_loss [1], log_alpha_grad [1],
+ * sumsq_partials: one sum of squares per workgroup of the third launch, H / 64 + (L - 1) (H / 16) (H /
+ * 128) + H / 128 of them for the actor's H and L, under pd_sac_critic_grad's protocol for *n_partials.
+ * Domain: pd_sac_actor's (state_dim <= 16, action_dim <= 8, hidden 128 / 256 / 512, 1 to 8 hidden
+ * layers) and, unless dheads_in is given, pd_sac_critic's with input state_dim + action_dim <= 16;
+ * parameters and gradients 16-byte aligned.  PD_ERR_INVALID: a negative batch, a dimension below 1, pitch
+ * below state_dim, a null required pointer, sumsq_partials without n_partials or too short, scratch
+ * missing, misaligned or short; PD_ERR_UNSUPPORTED: a dimension or layer count above the domain, another
+ * hidden width, a misaligned parameter or gradient; all before any launch.  batch == 0: PD_OK, nothing
+ * launched. */
+pd_status pd_sac_actor_grad(int64_t batch, int32_t state_dim, int32_t action_dim, const float* rows, int32_t pitch,
+                            const float* weights, int32_t actor_hidden, int32_t actor_layers,
+                            const float* const* actor_params, float* const* actor_grads, float log_std_min,
+                            float log_std_max, float max_action, int32_t critic_hidden, int32_t critic_layers,
+                            const float* const* params_q1, const float* const* params_q2, const float* log_alpha,
+                            float target_entropy, uint64_t seed, uint64_t draw, const float* eps_in,
+                            const float* dheads_in, float* new_actions, float* log_prob, float* q, float* heads,
+                            float* eps_out, float* dq_da, float* dheads_out, float* actor_loss, float* alpha_loss,
+                            float* log_alpha_grad, float* sumsq_partials, int32_t* n_partials, void* scratch,
+                            size_t scratch_bytes, void* stream);
 /* Insert the aero neighbourhoods solved on device and still queued into the handle's tables
  * (one tiny kernel; a no-op when nothing is queued).  Since ABI 10 every step launch (pd_step,
  * pd_step_n, pd_step_sac*, pd_rollout) inserts the neighbourhoods it solved itself, by its last

@@ -336,6 +336,7 @@ constexpr uint32_t kTagSacEps = 19;    // +a/2: pd_step_sac_ring's rsample noise
 // (32: kTagPso, the PSO update's r1, r2 -- pdpso.hip)
 constexpr uint32_t kTagPer = 48;       // pd_per_sample's uniforms: counter (item >> 1, draw lo, draw hi), items 2m, 2m + 1
 constexpr uint32_t kTagTdEps = 64;     // +k/2: pd_sac_td_target's rsample noise of components k, k+1: counter (row, draw lo, draw hi)
+constexpr uint32_t kTagActEps = 72;    // +k/2: pd_sac_actor_grad's rsample noise, the same counter: independent of the TD target's
 // randint(50, 99) - 50 from one Philox word: floor(49 u / 2^32) (multiply-shift; bias < 1.2e-8)
 PD_HD int prof_draw(uint32_t u) { return (int)(((uint64_t)u * 49u) >> 32); }
 

@@ -33,7 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pdenv.h"
-#include "pd_sac_mlp.h"
+#include "pd_sac_bwd.h"
 
 namespace {
 
@@ -168,6 +168,8 @@ __global__ __launch_bounds__(kSacBlock) void k_critic_rows(RowArgs a) {
         }
     }
     __syncthreads();
+    // (this loop and pd_sac_bwd.h's sac_bwd_hidden are the same chain and must be kept in step: routed
+    // through that function this kernel compiled to other register counts, so it keeps its copy)
     // ---- the hidden layers' backward on MFMA: delta_{l-1} = (delta_l . W_l) (h_{l-1} > 0); the 16
     // rows are the MFMA's rows, wave w the column tiles w, w + 4, ..., NT at a time; k runs over
     // W_l's rows in blocks of 32, lane group q taking k = 32 b + 8 q + j as in the forward pass
@@ -238,37 +240,7 @@ struct WArgs {
     float* sumsq;
 };
 
-// One wave's tile of dW = A^T . B over the batch: lane (r, q) gives the left operand's column r
-// and the right operand's column r of row b0 + q; four rows an instruction, ascending.  acc[i][m]
-// = dW[row 4 q + m][column r of tile i]; accb[m] = the left operand's column sums (against ones)
-template <int NT, typename FA, typename FB>
-__device__ __forceinline__ void wave_wgrad(int64_t bp, bool bias, FA&& fa, FB&& fb, f32x4 (&acc)[NT], f32x4& accb) {
-#pragma unroll
-    for (int i = 0; i < NT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    accb = f32x4{0.f, 0.f, 0.f, 0.f};
-    // U instructions' operands requested together, then the U (NT + 1) MFMAs in row order: the loop
-    // is bound by the latency of its loads (a workgroup a CU, nothing else to run meanwhile)
-    auto rows = [&](int64_t b0, auto uc) {
-        constexpr int U = decltype(uc)::value;
-        float av[U], bvv[U][NT];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            av[u] = fa(b0 + 4 * u);
-#pragma unroll
-            for (int i = 0; i < NT; ++i) bvv[u][i] = fb(b0 + 4 * u, i);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-#pragma unroll
-            for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bvv[u][i], acc[i], 0, 0, 0);
-            if (bias) accb = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], 1.f, accb, 0, 0, 0);
-        }
-    };
-    int64_t b0 = 0;
-    for (; b0 + 64 <= bp; b0 += 64) rows(b0, std::integral_constant<int, 16>{});
-    for (; b0 < bp; b0 += 16) rows(b0, std::integral_constant<int, 4>{});
-}
-
+// (wave_wgrad, one wave's tile of dW = A^T . B over the batch: pd_sac_bwd.h, shared with pdsacact.hip)
 template <int H>
 __global__ __launch_bounds__(kSacBlock) void k_critic_wgrad(WArgs a) {
     __shared__ float s_ss[4];

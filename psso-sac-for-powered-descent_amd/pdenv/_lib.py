@@ -104,7 +104,8 @@ EXPORTS = ["pd_abi_version", "pd_sizeof_params", "pd_sizeof_config", "pd_last_er
            "pd_pso_swarm_minima_scratch_bytes", "pd_step_n_info", "pd_pso_step_chunked", "pd_rollout_policy_chunked",
            "pd_rollout_sac", "pd_atm_table_lds", "pd_wind_slopes", "pd_collect_sac", "pd_per_sample_scratch_bytes",
            "pd_per_sample", "pd_per_update", "pd_sac_critic", "pd_sac_td_target",
-           "pd_sac_critic_grad_scratch_bytes", "pd_sac_critic_grad", "pd_adam_step"]
+           "pd_sac_critic_grad_scratch_bytes", "pd_sac_critic_grad", "pd_adam_step", "pd_sac_critic_dinput",
+           "pd_sac_actor_grad_scratch_bytes", "pd_sac_actor_grad"]
 SAC_LOSS_L2, SAC_LOSS_L1 = 0, 1   # PD_SAC_LOSS_*
 ADAM_MAX_TENSORS = 64             # PD_ADAM_MAX_TENSORS
 PER_MAX_BATCH = 1024              # PD_PER_MAX_BATCH
@@ -167,6 +168,14 @@ def load(path=None):
     L.pd_sac_critic_grad.restype = C.c_int
     L.pd_adam_step.argtypes = [I32, vp, vp, vp, vp, P(I64), vp, D, D, D, D, D, D, vp, I32, vp, D, vp]
     L.pd_adam_step.restype = C.c_int
+    L.pd_sac_critic_dinput.argtypes = [I64, I32, I32, I32, I32, vp, I32, vp, vp, vp, vp, vp]
+    L.pd_sac_critic_dinput.restype = C.c_int
+    L.pd_sac_actor_grad_scratch_bytes.argtypes = [I64, I32, I32, I32]
+    L.pd_sac_actor_grad_scratch_bytes.restype = C.c_size_t
+    L.pd_sac_actor_grad.argtypes = [I64, I32, I32, vp, I32, vp, I32, I32, vp, vp, F32, F32, F32, I32, I32, vp, vp, vp,
+                                    F32, U64, U64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(I32), vp,
+                                    C.c_size_t, vp]
+    L.pd_sac_actor_grad.restype = C.c_int
     L.pd_set_tuning.argtypes = [vp, P(PdTuning)]
     L.pd_get_tuning.argtypes = [vp, P(PdTuning)]
     L.pd_rollout.argtypes = [vp, vp, I32, vp, vp]

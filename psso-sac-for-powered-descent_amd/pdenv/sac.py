@@ -439,18 +439,20 @@ class CriticKernel:
 
 
 _TAG_TD_EPS = 64                  # kTagTdEps (csrc/pd_common.h)
+_TAG_ACT_EPS = 72                 # kTagActEps
 
 
-def td_eps(seed, draw, batch, action_dim, device):
+def td_eps(seed, draw, batch, action_dim, device, tag=_TAG_TD_EPS):
     """pd_sac_td_target's eps draws [batch, A] as torch expressions (the fallback's eps source):
     the same Philox4x32-10 blocks and the same Box-Muller in binary64 (torch's log, cos and sin in
-    place of the kernel's), cast to float32 -- the kernel's values to float32 rounding."""
+    place of the kernel's), cast to float32 -- the kernel's values to float32 rounding.  tag: the
+    Philox purpose tag (pd_sac_actor_grad's draws: _TAG_ACT_EPS)."""
     i64 = dict(dtype=torch.int64, device=device)
     mask = 0xFFFFFFFF
     pairs = (action_dim + 1) // 2
     row = torch.arange(batch, **i64)[:, None].expand(batch, pairs)
     c = [row & mask, torch.full_like(row, draw & mask), torch.full_like(row, (draw >> 32) & mask),
-         (_TAG_TD_EPS + torch.arange(pairs, **i64))[None, :].expand(batch, pairs)]
+         (tag + torch.arange(pairs, **i64))[None, :].expand(batch, pairs)]
     k0, k1 = seed & mask, (seed >> 32) & mask
     for _ in range(10):                                    # (int64 products wrap: the low 64 bits are exact)
         p0, p1 = c[0] * 0xD2511F53, c[2] * 0xCD9E8D57
@@ -561,6 +563,53 @@ class TdTarget:
         return out.reshape(B, 1)
 
 
+def _adam_reasons(optimizer, params):
+    """Why pd_adam_step does not take this optimizer over exactly `params`: a list of words, empty
+    for a plain torch.optim.Adam with one param group -- "adam", "param_groups", "params",
+    "weight_decay", "amsgrad", "maximize", "capturable", "fused", "differentiable", "lr"."""
+    if type(optimizer) is not torch.optim.Adam:
+        return ["adam"]
+    if len(optimizer.param_groups) != 1:
+        return ["param_groups"]
+    why = []
+    g = optimizer.param_groups[0]
+    if len(params) > L.ADAM_MAX_TENSORS or len(g["params"]) != len(params) or not all(
+            a is b for a, b in zip(g["params"], params)):
+        why.append("params")
+    if g.get("weight_decay", 0) != 0:
+        why.append("weight_decay")
+    why += [k for k in ("amsgrad", "maximize", "capturable", "fused", "differentiable") if g.get(k)]
+    if isinstance(g["lr"], torch.Tensor):
+        why.append("lr")
+    return why
+
+
+def _adam_ensure_state(optimizer, params):
+    """torch.optim.Adam's state of `params`, created if empty (as Adam._init_group does), `step` a
+    host tensor."""
+    st = optimizer.state
+    for p in params:
+        s = st[p]
+        if len(s) == 0:
+            s["step"] = torch.tensor(0.0, dtype=torch.float32)
+            s["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            s["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        elif s["step"].is_cuda:
+            s["step"] = s["step"].cpu()
+
+
+def _adam_advance(optimizer, params):
+    """Advance every tensor's `step` (a host tensor: no device work); (step_size, bc2_sqrt, beta1,
+    beta2, eps) as pd_adam_step takes them, from param_groups as they are now."""
+    st, g = optimizer.state, optimizer.param_groups[0]
+    for p in params:
+        st[p]["step"] += 1
+    t = int(st[params[0]]["step"].item())
+    beta1, beta2 = g["betas"]
+    bc1, bc2 = 1 - beta1 ** t, 1 - beta2 ** t
+    return float(g["lr"]) / bc1, bc2 ** 0.5, beta1, beta2, float(g["eps"])
+
+
 class CriticUpdate:
     """The critic step of SACPyTorch.update as three launches and no host synchronisation
     (csrc/pdsacupd.hip): critic(states, actions), the loss of sac_pytorch.py:457-468 (MSE or L1, with
@@ -642,20 +691,7 @@ class CriticUpdate:
                 why.append("target")
             elif "tensors" not in why and not CriticKernel.supported(critic_target):
                 why.append("target")
-        if type(optimizer) is not torch.optim.Adam:
-            return why + ["adam"]
-        if len(optimizer.param_groups) != 1:
-            return why + ["param_groups"]
-        g = optimizer.param_groups[0]
-        if len(params) > L.ADAM_MAX_TENSORS or len(g["params"]) != len(params) or not all(
-                a is b for a, b in zip(g["params"], params)):
-            why.append("params")
-        if g.get("weight_decay", 0) != 0:
-            why.append("weight_decay")
-        why += [k for k in ("amsgrad", "maximize", "capturable", "fused", "differentiable") if g.get(k)]
-        if isinstance(g["lr"], torch.Tensor):
-            why.append("lr")
-        return why
+        return why + _adam_reasons(optimizer, params)
 
     @staticmethod
     def supported(critic, optimizer, critic_target=None):
@@ -738,35 +774,20 @@ class CriticUpdate:
         self.q, self.critic_loss = o["q"], (o["loss"] if want else None)
         return o["td_abs"] if want else None
 
-    def _ensure_state(self):
-        st = self.optimizer.state
-        for p in self.params:
-            s = st[p]
-            if len(s) == 0:
-                s["step"] = torch.tensor(0.0, dtype=torch.float32)
-                s["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                s["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            elif s["step"].is_cuda:
-                s["step"] = s["step"].cpu()
-
     def _kernel_step(self, B, dev):
-        self._ensure_state()
-        st, g = self.optimizer.state, self.optimizer.param_groups[0]
+        _adam_ensure_state(self.optimizer, self.params)
+        step_size, bc2_sqrt, beta1, beta2, eps = _adam_advance(self.optimizer, self.params)
+        st = self.optimizer.state
         lp, lg, lm, lv, lt = self._lists
         for k, (p, tp) in enumerate(zip(self.params, self.targets)):
             s = st[p]
-            s["step"] += 1                                   # (a host tensor: no device work)
             lp[k], lg[k], lt[k] = p.data_ptr(), p.grad.data_ptr(), tp.data_ptr()
             lm[k], lv[k] = s["exp_avg"].data_ptr(), s["exp_avg_sq"].data_ptr()
-        t = int(st[self.params[0]]["step"].item())
-        beta1, beta2 = g["betas"]
-        bc1, bc2 = 1 - beta1 ** t, 1 - beta2 ** t
         o = self._buffers(B, dev)
         clip = self.max_grad_norm is not None
-        L.check(self.lib.pd_adam_step(len(self.params), lp, lg, lm, lv, self._numel, lt, float(g["lr"]) / bc1,
-                                      bc2 ** 0.5, beta1, beta2, float(g["eps"]),
-                                      self.max_grad_norm if clip else 0.0, _ptr(o["partials"]), self.n_partials,
-                                      _ptr(o["grad_norm"]), self.tau, _stream(dev)))
+        L.check(self.lib.pd_adam_step(len(self.params), lp, lg, lm, lv, self._numel, lt, step_size, bc2_sqrt, beta1,
+                                      beta2, eps, self.max_grad_norm if clip else 0.0, _ptr(o["partials"]),
+                                      self.n_partials, _ptr(o["grad_norm"]), self.tau, _stream(dev)))
         self.grad_norm = o["grad_norm"] if clip else None
 
     def backward(self, rows, target_q, weights=None, dq=None):
@@ -785,6 +806,333 @@ class CriticUpdate:
         else:
             self._torch_step()
         return td_abs
+
+
+def _actor_shape(actor):
+    """(S, A, H, hidden layer count) of an Actor inside pd_sac_actor's shapes, else None."""
+    net = getattr(actor, "shared_net", None)
+    if not isinstance(net, nn.Sequential) or not isinstance(getattr(actor, "mean", None), nn.Linear) \
+            or not isinstance(getattr(actor, "log_std", None), nn.Linear):
+        return None
+    lins = [m for m in net if isinstance(m, nn.Linear)]
+    acts = [m for m in net if not isinstance(m, nn.Linear)]
+    if not lins or len(lins) > 8 or len(acts) != len(lins) or any(not isinstance(m, nn.ReLU) for m in acts):
+        return None
+    S, H, A = lins[0].in_features, lins[0].out_features, actor.mean.out_features
+    ok = (H in (128, 256, 512) and S <= 16 and A <= 8 and all(m.in_features == H and m.out_features == H for m in lins[1:])
+          and actor.mean.in_features == H and actor.log_std.in_features == H and actor.log_std.out_features == A)
+    return (S, A, H, len(lins)) if ok else None
+
+
+def _actor_dims(actor):
+    """(state_dim, action_dim) of an actor, inside pd_sac_actor's shapes or not (the torch path's): the
+    first Linear's inputs and the mean head's outputs."""
+    sh = _actor_shape(actor)
+    if sh is not None:
+        return sh[:2]
+    first = next((m for m in actor.modules() if isinstance(m, nn.Linear)), None)
+    mean = getattr(actor, "mean", None)
+    if first is None or not isinstance(mean, nn.Linear):
+        raise ValueError("ActorUpdate: an actor with a Linear layer and a Linear `mean` head is required")
+    return first.in_features, mean.out_features
+
+
+def _critic_shape(critic):
+    """(S + A, H, hidden layer count) of a twin critic inside pd_sac_critic's shapes, else None."""
+    shapes = []
+    for net in (getattr(critic, "q1", None), getattr(critic, "q2", None)):
+        hidden, last, ok = _q_linears(net) if isinstance(net, nn.Sequential) else ([], None, False)
+        if not ok or len(hidden) > 8:
+            return None
+        H = hidden[0].out_features
+        if not (H in (128, 256, 512) and 2 <= hidden[0].in_features <= 16 and last.out_features == 1
+                and last.in_features == H and all(m.in_features == H and m.out_features == H for m in hidden[1:])):
+            return None
+        shapes.append((hidden[0].in_features, H, len(hidden)))
+    return shapes[0] if shapes[0] == shapes[1] else None
+
+
+def _kernel_tensor(p):
+    return p.dtype == torch.float32 and p.is_cuda and p.is_contiguous() and p.data_ptr() % 16 == 0
+
+
+class ActorUpdate:
+    """The actor and temperature steps of SACPyTorch.update (sac_pytorch.py:485-521) as five launches
+    and no host synchronisation (csrc/pdsacact.hip): actor.sample(states), critic(states, new_actions)
+    with the critic as it is now (CriticUpdate has just stepped it), min(q1, q2), the actor loss with or
+    without PER weights, zero_grad() + backward() through both Q nets into the actor and the
+    temperature loss's gradient (pd_sac_actor_grad: three launches, the gradients land in p.grad,
+    overwritten), then clip_grad_norm_ and actor_optimizer.step() (pd_adam_step over the actor's
+    tensors) and alpha_optimizer.step() (pd_adam_step over the one-element log_alpha).
+
+    actor_optimizer: the caller's torch.optim.Adam over actor.parameters(); alpha_optimizer: the
+    caller's torch.optim.Adam over [log_alpha], or None for no entropy tuning (alpha_loss is then 0
+    and log_alpha and its .grad are untouched).  Their state is created if empty and then used in
+    place, as CriticUpdate does.  log_alpha: a one-element float32 device tensor that requires grad
+    (the reference's torch.tensor(np.log(0.2)) is float64: see reasons()).  target_entropy defaults
+    to -action_dim (sac_pytorch.py:321).
+
+    log_prob = upd(rows, weights=None, draw=None, eps=None): rows [B, >= S] float32 with unit column
+    stride whose first S columns are the state (buffer.last_rows, or packed states), weights [B] or
+    [B, 1] or None, eps [B, A] the rsample noise or None: drawn in the kernel from (seed, draw, row,
+    component) under a Philox tag of its own (72; TdTarget's is 64, so the same seed and draw give
+    independent noise), draw defaulting to a counter that advances by one per call.  Returns log_prob
+    [B, 1]; upd.new_actions [B, A], upd.q [B, 2], upd.actor_loss [1], upd.alpha_loss [1] and
+    upd.grad_norm [1] (None without max_grad_norm) are device tensors -- reading them is the caller's
+    synchronisation.  All are owned by the object per batch size and overwritten by the next call.
+    upd.backward(...) runs the forward and backward passes only (for another optimizer); its keyword
+    outputs heads, eps_out, dq_da, dheads_out receive the intermediate values, and dheads [B, 2A]
+    replaces the upstream gradient dLoss / d(mean | raw log_std) (no critic pass then).
+
+    One difference from the reference: actor_loss.backward() there also accumulates into the critic's
+    p.grad and into log_alpha.grad (both are zeroed before their next use).  Here the critic's p.grad
+    stays as CriticUpdate left it, and log_alpha.grad holds the temperature loss's gradient.
+
+    Where supported() is false the same steps run in torch (autograd, clip_grad_norm_, the optimizers'
+    own step()) on the same eps source and return the same things."""
+
+    def __init__(self, actor, critic, log_alpha, actor_optimizer, alpha_optimizer=None, target_entropy=None,
+                 max_grad_norm=None, seed=0):
+        self.actor, self.critic, self.log_alpha = actor, critic, log_alpha
+        self.actor_optimizer, self.alpha_optimizer = actor_optimizer, alpha_optimizer
+        self.S, self.A = _actor_dims(actor)
+        self.target_entropy = float(-self.A if target_entropy is None else target_entropy)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.seed, self.draws = int(seed), 0
+        self.kernel = self.supported(actor, critic, log_alpha, actor_optimizer, alpha_optimizer)
+        self.new_actions = self.q = self.actor_loss = self.alpha_loss = self.grad_norm = None
+        self._out = {}
+        if self.kernel:
+            self.lib = L.load()
+            self.ak, self.ck = ActorKernel(actor), CriticKernel(critic)
+            self.params = list(self.ak.params)
+            n, vp = len(self.params), C.c_void_p
+            self._g = (vp * n)()
+            self._lists = tuple((vp * n)() for _ in range(4))      # params, grads, exp_avg, exp_avg_sq
+            self._numel = (C.c_int64 * n)(*[p.numel() for p in self.params])
+            self._alpha_lists = tuple((vp * 1)() for _ in range(4))
+            self._one = (C.c_int64 * 1)(1)
+            H, nl = self.ak.H, self.ak.nl
+            self.n_partials = H // 64 + (nl - 1) * (H // 16) * (H // 128) + H // 128
+            self._np = C.c_int32(0)
+
+    @staticmethod
+    def reasons(actor, critic, log_alpha, actor_optimizer, alpha_optimizer=None):
+        """Why the kernel path does not take these: a list of words, empty when supported -- "actor"
+        (not pd_sac_actor's shapes: Linear-ReLU stack, hidden 128 / 256 / 512, <= 8 hidden layers, S <=
+        16, A <= 8), "critic" (not two Linear-ReLU stacks of equal shape inside pd_sac_critic's, or
+        their input is not S + A), "tensors" (a parameter not contiguous float32 on the device, 16-byte
+        aligned), "log_alpha" (not a one-element float32 device tensor: the reference's
+        torch.tensor(np.log(0.2)) is float64), the actor optimizer's words (CriticUpdate.reasons) and
+        the temperature optimizer's with the prefix "alpha_"."""
+        why = []
+        ash, csh = _actor_shape(actor), _critic_shape(critic)
+        if ash is None:
+            why.append("actor")
+        if csh is None or (ash is not None and csh[0] != ash[0] + ash[1]):
+            why.append("critic")
+        if not all(_kernel_tensor(p) for p in list(actor.parameters()) + list(critic.parameters())):
+            why.append("tensors")
+        if not (isinstance(log_alpha, torch.Tensor) and log_alpha.dtype == torch.float32 and log_alpha.is_cuda
+                and log_alpha.numel() == 1):
+            why.append("log_alpha")
+        if ash is not None:
+            lins = [m for m in actor.shared_net if isinstance(m, nn.Linear)] + [actor.mean, actor.log_std]
+            why += _adam_reasons(actor_optimizer, [t for m in lins for t in (m.weight, m.bias)])
+        elif type(actor_optimizer) is not torch.optim.Adam:
+            why.append("adam")
+        if alpha_optimizer is not None:
+            why += ["alpha_" + w for w in _adam_reasons(alpha_optimizer, [log_alpha])]
+        return why
+
+    @staticmethod
+    def supported(actor, critic, log_alpha, actor_optimizer, alpha_optimizer=None):
+        return not ActorUpdate.reasons(actor, critic, log_alpha, actor_optimizer, alpha_optimizer)
+
+    def _draw(self, draw, eps):
+        if eps is not None:
+            return 0
+        if draw is None:
+            draw = self.draws
+            self.draws += 1
+        return int(draw) & (2 ** 64 - 1)
+
+    def _buffers(self, B, dev):
+        out = self._out.get(B)
+        if out is None:
+            f32 = dict(dtype=torch.float32, device=dev)
+            out = dict(new_actions=torch.empty(B, self.A, **f32), log_prob=torch.empty(B, 1, **f32),
+                       q=torch.empty(B, 2, **f32), actor_loss=torch.zeros(1, **f32), alpha_loss=torch.zeros(1, **f32),
+                       grad_norm=torch.empty(1, **f32))
+            if self.kernel:
+                nbytes = int(self.lib.pd_sac_actor_grad_scratch_bytes(B, self.A, self.ak.H, self.ak.nl))
+                out.update(partials=torch.empty(self.n_partials, **f32), scratch=torch.empty((nbytes + 3) // 4, **f32))
+            self._out[B] = out
+        return out
+
+    # ---- the torch path
+    def _torch_backward(self, rows, weights, draw, eps, outs, dheads):
+        a, B, S, A = self.actor, int(rows.shape[0]), self.S, self.A
+        o = self._buffers(B, rows.device)
+        if eps is None:
+            eps = td_eps(self.seed & (2 ** 64 - 1), draw, B, A, rows.device, tag=_TAG_ACT_EPS)
+        states = rows[:, :S]
+        w = None if weights is None else weights.detach().reshape(B, 1)
+        if isinstance(getattr(a, "shared_net", None), nn.Module) and isinstance(getattr(a, "log_std", None), nn.Module):
+            f = a.shared_net(states)
+            mean, raw = a.mean(f), a.log_std(f)
+            ls = torch.clamp(raw, a.log_std_min, a.log_std_max)
+        else:                      # (an actor of another build: its own forward; `heads` then holds the clamped log_std)
+            mean, ls = a(states)
+            raw = ls
+        sd = ls.exp()
+        x = mean + sd * eps
+        act = torch.tanh(x)
+        lp = (-((x - mean) ** 2) / (2 * sd ** 2) - ls - 0.9189385332046727
+              - torch.log(1 - act.pow(2) + 1e-6)).sum(-1, keepdim=True)
+        na = act * a.max_action
+        params = list(a.parameters())
+        self.actor_optimizer.zero_grad()
+        got = dict(heads=torch.cat([mean, raw], dim=1), eps_out=eps)
+        if dheads is not None:
+            grads = torch.autograd.grad([mean, raw], params, [dheads[:, :A], dheads[:, A:]], allow_unused=True)
+        else:
+            if outs.get("dq_da") is not None:
+                na = na.detach().requires_grad_(True)       # (a leaf, for the Q nets' input gradient alone)
+                q1, q2 = self.critic(states, na)
+                got["dq_da"] = torch.stack([torch.autograd.grad(q1.sum(), na, retain_graph=True)[0],
+                                            torch.autograd.grad(q2.sum(), na)[0]], dim=1)
+                na = act * a.max_action
+            q1, q2 = self.critic(states, na)
+            alpha = self.log_alpha.detach().exp()
+            t = alpha * lp - torch.min(q1, q2)
+            loss = (t if w is None else w * t).mean()
+            heads_g = torch.autograd.grad(loss, [mean, raw], retain_graph=True)
+            got["dheads_out"] = torch.cat(heads_g, dim=1)
+            grads = torch.autograd.grad(loss, params, allow_unused=True)
+            o["q"].copy_(torch.cat([q1, q2], dim=1).detach())
+            o["actor_loss"].copy_(loss.detach().reshape(1))
+        for p, g in zip(params, grads):
+            p.grad = torch.zeros_like(p) if g is None else g.detach().to(p.dtype)
+        if self.alpha_optimizer is not None:
+            t = (lp + self.target_entropy).detach()
+            g = -(t if w is None else w * t).mean()
+            self.log_alpha.grad = g.to(self.log_alpha.dtype).reshape(self.log_alpha.shape)
+            o["alpha_loss"].copy_((self.log_alpha.detach().reshape(()) * g).reshape(1))
+        o["new_actions"].copy_(na.detach())
+        o["log_prob"].copy_(lp.detach())
+        for name, v in got.items():
+            if outs.get(name) is not None:
+                outs[name].copy_(v.detach().reshape(outs[name].shape))
+
+    def _torch_step(self):
+        self.grad_norm = None
+        if self.max_grad_norm is not None:
+            self.grad_norm = torch.nn.utils.clip_grad_norm_(self.actor.parameters(),
+                                                            max_norm=self.max_grad_norm).reshape(1)
+        self.actor_optimizer.step()
+        if self.alpha_optimizer is not None:
+            self.alpha_optimizer.step()
+
+    # ---- the kernel path
+    def _grad_ptrs(self):
+        for k, p in enumerate(self.params):
+            if p.grad is None or not (p.grad.is_contiguous() and p.grad.dtype == torch.float32):
+                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            self._g[k] = p.grad.data_ptr()
+        return self._g
+
+    def _kernel_backward(self, rows, weights, draw, eps, outs, dheads):
+        B = int(rows.shape[0])
+        for t, cols in ((weights, 1), (eps, self.A), (dheads, 2 * self.A), (outs.get("heads"), 2 * self.A),
+                        (outs.get("eps_out"), self.A), (outs.get("dq_da"), 2 * self.A),
+                        (outs.get("dheads_out"), 2 * self.A)):
+            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B * cols):
+                raise ValueError("ActorUpdate: contiguous float32 tensors of the batch's length are required")
+        if not (rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[1] >= self.S
+                and (B == 0 or rows.stride(1) == 1)):
+            raise ValueError("ActorUpdate: rows [B, >= S] float32 with unit column stride are required")
+        o = self._buffers(B, rows.device)
+        a, ak, ck = self.actor, self.ak, self.ck
+        p1, p2 = ck.ptrs()
+        self._np.value = self.n_partials
+        tune = self.alpha_optimizer is not None
+        la = self.log_alpha
+        if tune and (la.grad is None or la.grad.dtype != torch.float32):
+            la.grad = torch.zeros_like(la)
+        L.check(self.lib.pd_sac_actor_grad(
+            B, ak.S, ak.A, _ptr(rows), int(rows.stride(0)) if B else ak.S, _ptr(weights), ak.H, ak.nl, ak.ptrs(),
+            self._grad_ptrs(), a.log_std_min, a.log_std_max, a.max_action, ck.H, ck.nl, p1, p2, _ptr(la),
+            self.target_entropy, self.seed & (2 ** 64 - 1), draw, _ptr(eps), _ptr(dheads), _ptr(o["new_actions"]),
+            _ptr(o["log_prob"]), _ptr(o["q"]), _ptr(outs.get("heads")), _ptr(outs.get("eps_out")),
+            _ptr(outs.get("dq_da")), _ptr(outs.get("dheads_out")), _ptr(o["actor_loss"]),
+            _ptr(o["alpha_loss"]) if tune else None, _ptr(la.grad) if tune else None, _ptr(o["partials"]),
+            C.byref(self._np), _ptr(o["scratch"]), o["scratch"].numel() * 4, _stream(rows.device)))
+
+    def _kernel_step(self, B, dev):
+        o = self._buffers(B, dev)
+        clip = self.max_grad_norm is not None
+        opt = self.actor_optimizer
+        _adam_ensure_state(opt, self.params)
+        step_size, bc2_sqrt, beta1, beta2, eps = _adam_advance(opt, self.params)
+        lp, lg, lm, lv = self._lists
+        for k, p in enumerate(self.params):
+            s = opt.state[p]
+            lp[k], lg[k] = p.data_ptr(), p.grad.data_ptr()
+            lm[k], lv[k] = s["exp_avg"].data_ptr(), s["exp_avg_sq"].data_ptr()
+        L.check(self.lib.pd_adam_step(len(self.params), lp, lg, lm, lv, self._numel, None, step_size, bc2_sqrt, beta1,
+                                      beta2, eps, self.max_grad_norm if clip else 0.0, _ptr(o["partials"]),
+                                      self.n_partials, _ptr(o["grad_norm"]), 0.0, _stream(dev)))
+        self.grad_norm = o["grad_norm"] if clip else None
+        opt = self.alpha_optimizer
+        if opt is not None:
+            la = self.log_alpha
+            _adam_ensure_state(opt, [la])
+            step_size, bc2_sqrt, beta1, beta2, eps = _adam_advance(opt, [la])
+            s = opt.state[la]
+            lp, lg, lm, lv = self._alpha_lists
+            lp[0], lg[0], lm[0], lv[0] = la.data_ptr(), la.grad.data_ptr(), s["exp_avg"].data_ptr(), s["exp_avg_sq"].data_ptr()
+            L.check(self.lib.pd_adam_step(1, lp, lg, lm, lv, self._one, None, step_size, bc2_sqrt, beta1, beta2, eps, 0.0,
+                                          None, 0, None, 0.0, _stream(dev)))
+
+    def backward(self, rows, weights=None, draw=None, eps=None, dheads=None, heads=None, eps_out=None, dq_da=None,
+                 dheads_out=None):
+        """The forward and backward passes alone: the actor's gradients in p.grad (overwritten),
+        log_alpha.grad set (with an alpha_optimizer), new_actions, q, actor_loss and alpha_loss set;
+        returns log_prob [B, 1]."""
+        B = int(rows.shape[0])
+        draw = self._draw(draw, eps)
+        outs = dict(heads=heads, eps_out=eps_out, dq_da=dq_da, dheads_out=dheads_out)
+        if self.kernel:
+            self._kernel_backward(rows, weights, draw, eps, outs, dheads)
+        else:
+            self._torch_backward(rows, weights, draw, eps, outs, dheads)
+        o = self._buffers(B, rows.device)
+        self.new_actions, self.q, self.actor_loss, self.alpha_loss = o["new_actions"], o["q"], o["actor_loss"], o["alpha_loss"]
+        return o["log_prob"]
+
+    def __call__(self, rows, weights=None, draw=None, eps=None):
+        log_prob = self.backward(rows, weights, draw, eps)
+        if int(rows.shape[0]) == 0:
+            return log_prob
+        if self.kernel:
+            self._kernel_step(int(rows.shape[0]), rows.device)
+        else:
+            self._torch_step()
+        return log_prob
+
+
+def sac_update(buffer, td_target, critic_update, actor_update, batch_size):
+    """One learner update in the order of SACPyTorch.update (sac_pytorch.py:411-531) on a prioritized
+    buffer: sample, TdTarget, CriticUpdate, ActorUpdate, update_priorities.  With a
+    KernelPrioritizedReplayBuffer and the three objects on their kernel paths this is a fixed sequence
+    of launches on device pointers: nothing is read back and nothing is returned."""
+    _, _, _, _, _, weights, indices = buffer.sample(batch_size)
+    rows = buffer.last_rows
+    target_q = td_target(rows)
+    td_abs = critic_update(rows, target_q, weights)
+    actor_update(rows, weights)
+    buffer.update_priorities(indices, td_abs)
 
 
 class SACCollector:
