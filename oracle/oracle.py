@@ -34,6 +34,9 @@ INFO_NAMES = ["air_density", "atmospheric_pressure", "speed_of_sound", "mach_num
               "control_force_perpendicular", "control_moment_z", "aero_force_x", "aero_force_y",
               "ug", "vg", "g_load_1_sec_window", "C_a", "C_n_L", "gimbal_angle_deg",
               "delta_command_left_rad", "delta_command_right_rad", "drag", "lift"]
+# orc_wind_info: the wind terms of the last sub-step, merged into the info dicts below (the info
+# array itself keeps its length: orc_out is part of the library's binary interface)
+WIND_INFO_NAMES = ["acceleration_x_component_wind", "acceleration_y_component_wind", "M_wind_z"]
 
 
 class OrcParams(C.Structure):
@@ -87,6 +90,13 @@ class OrcU32x4(C.Structure):
     _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("z", C.c_uint32), ("w", C.c_uint32)]
 
 
+def wind_info():
+    """The wind terms of this thread's last physics sub-step (orc_wind_info) as a dict."""
+    w = (D * 3)()
+    lib().orc_wind_info(w)
+    return dict(zip(WIND_INFO_NAMES, w[:]))
+
+
 def build():
     """Compile oracle/pd_oracle.c (gcc).  Building the checker is not using it."""
     subprocess.run(["make", "-s", "-C", HERE], check=True)
@@ -120,6 +130,8 @@ def lib():
         L.orc_step.argtypes = [P(OrcParams), P(OrcEnv), C.c_int, C.c_int, P(D), C.c_int, P(D), P(OrcOut)]
         L.orc_physics.restype = C.c_int
         L.orc_physics.argtypes = [P(OrcParams), P(OrcEnv), C.c_int, P(D), C.c_int, P(D), P(D)]
+        L.orc_wind_info.restype = None
+        L.orc_wind_info.argtypes = [P(D)]
         L.orc_rollout_ex.restype = D
         L.orc_rollout_ex.argtypes = [P(OrcParams), C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float),
                                      C.c_int, C.c_int, D, C.c_uint64, P(C.c_int64)]
@@ -271,7 +283,7 @@ class Oracle:
         nz = None if noise is None else (D * 8)(*[float(v) for v in np.asarray(noise).ravel()])
         o = OrcOut()
         self.L.orc_step(C.byref(self.P), C.byref(self.E), self.phase, self.rtd, ua, int(f32), nz, C.byref(o))
-        info = dict(zip(INFO_NAMES, o.info[:]))
+        info = dict(zip(INFO_NAMES, o.info[:]), **wind_info())
         nobs = OBS_DIM_RL[self.phase] if self.rtd != RTD_PSO else (2 if self.phase == PURE_THROTTLE else 5)
         return (np.array(self.E.s[:]), o.reward, bool(o.done), bool(o.trunc), int(o.trunc_id),
                 np.array(o.obs[:nobs]), info)
@@ -286,7 +298,7 @@ class Oracle:
         ua = (D * 4)(*list(a) + [0.0] * (4 - len(a)))
         info = (D * len(INFO_NAMES))()
         self.L.orc_physics(C.byref(self.P), C.byref(self.E), self.phase, ua, int(f32), None, info)
-        return np.array(self.E.s[:]), dict(zip(INFO_NAMES, info[:]))
+        return np.array(self.E.s[:]), dict(zip(INFO_NAMES, info[:]), **wind_info())
 
 
 _P_cache = {}

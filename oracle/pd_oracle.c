@@ -388,6 +388,9 @@ static void vk_step(const double* Ad, const double* Bd, double sigma, double* s,
 static uint8_t* g_qlog;
 static __thread uint8_t* g_qlog_step;
 void orc_set_qlog(uint8_t* buf) { g_qlog = buf; }
+/* wind terms of this thread's last sub-step that filled an info array (orc_wind_info) */
+static __thread double g_wind_last[3];
+void orc_wind_info(double out[3]) { memcpy(out, g_wind_last, sizeof(g_wind_last)); }
 
 static void substep(const orc_params* P, orc_env* E, int phase, const double* u, int f32,
                     double dt, double dt_act, const double* noise2, double* info, double* kout) {
@@ -667,6 +670,9 @@ static void substep(const orc_params* P, orc_env* E, int phase, const double* u,
     mp -= mdot_dt; m -= mdot_dt; t += dt;
     s[0] = x; s[1] = y; s[2] = vx; s[3] = vy; s[4] = th; s[5] = thd; s[6] = ga; s[7] = al;
     s[8] = m; s[9] = mp; s[10] = t;
+    if (info) {   /* rockets_physics.py:660-661 divide by the mass after its update (:642) */
+        g_wind_last[0] = Fwx / m; g_wind_last[1] = Fwy / m; g_wind_last[2] = Mw;
+    }
 }
 
 int orc_physics(const orc_params* P, orc_env* E, int phase, const double* u, int f32,

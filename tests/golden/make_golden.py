@@ -432,6 +432,161 @@ def phases(rp, rl_env_cls):
     save("ref_phases.npz", **out)
 
 
+@contextlib.contextmanager
+def injected_noise(normals, uniforms):
+    """np.random.randn (one per von Karman filter step, vonkarman.py:34) and random.uniform (the
+    sigmas of _new_filters, vonkarman.py:62-63) replaced by recorded streams; yields the counters
+    {"n": normals consumed, "u": uniforms consumed}.  Uniforms past the given ones: the midpoint."""
+    cnt = {"n": 0, "u": 0}
+    orig_randn, orig_uniform = np.random.randn, random.uniform
+
+    def fake_randn(*a):
+        v = normals[cnt["n"]]; cnt["n"] += 1
+        return v
+
+    def fake_uniform(a, b):
+        v = uniforms[cnt["u"]] if cnt["u"] < len(uniforms) else a + (b - a) * 0.5
+        cnt["u"] += 1
+        return v
+
+    np.random.randn, random.uniform = fake_randn, fake_uniform
+    try:
+        yield cnt
+    finally:
+        np.random.randn, random.uniform = orig_randn, orig_uniform
+
+
+WIND_INFO = ["acceleration_x_component_wind", "acceleration_y_component_wind", "M_wind_z", "mass_flow",
+             "air_density", "mach_number", "CL", "CD", "gimbal_angle_deg", "d_cp_cg"]
+
+
+def phases_wind(rp, rl_env_cls):
+    """Wind (full_wind_model.WindModel: percentile profile + von Karman gusts below 15 km) on the
+    five phases besides the two landing burns, which phases() and wind_episodes() leave out.
+
+    (a) 120 teacher-forced compile_physics steps per phase from states of the phase's recorded
+    run: rows with i % 4 < 2 get an altitude U(300, 14 500) m inside the gust band, the others keep
+    theirs (at least 20 of them above the 15 km ceiling, placed at U(15 500, 40 000) m where the
+    recorded run has too few).  Rows 0..99: stochastic wind, a fresh WindModel per row with the
+    percentile cycling over ints and floats, injected sigmas, N(0, 1) filter pre-states and 8
+    injected normals; rows 100..119: the same with stochastic_wind=False.
+    (b) one windy rl_wrapped_env_pytorch episode per RL-steppable phase (noise injected as in
+    wind_episodes, actions of phases()' second spec), at most 300 steps."""
+    from src.envs.wind.full_wind_model import WindModel
+    out = {}
+    pcts = [50, 57.0, 75, 88.0, 99]      # wrappers pass an int, WindModel draws float(randint)
+    n_rows, n_stoch = 120, 100
+    for k, (tag, phase, A) in enumerate((("pc", "landing_burn_pure_throttle_Pcontrol", 1),
+                                         ("ba", "ballistic_arc_descent", 1), ("fl", "flip_over_boostbackburn", 1),
+                                         ("sub", "subsonic", 2), ("sup", "supersonic", 2))):
+        rng = np.random.default_rng(3100 + k)
+        fn = rp.compile_physics(0.1, phase)
+        pool, _ = phase_states(phase)
+        S = pool[rng.choice(len(pool), n_rows, replace=len(pool) < n_rows)].copy()
+        band = np.arange(n_rows) % 4 < 2
+        S[band, 1] = rng.uniform(300.0, 14500.0, int(band.sum()))
+        keep = np.nonzero(~band)[0]
+        lows = keep[S[keep, 1] <= 15000.0]
+        need = 20 - (len(keep) - len(lows))
+        if need > 0:
+            place = lows[np.linspace(0, len(lows) - 1, need).astype(int)]
+            S[place, 1] = rng.uniform(15500.0, 40000.0, need)
+        assert int((S[band, 1] < 14500.0).sum()) == n_rows // 2, tag
+        assert int((S[~band, 1] > 15000.0).sum()) >= 20, tag
+        assert int((S[:n_stoch][~band[:n_stoch], 1] > 15000.0).sum()) >= 10, tag
+        if phase == "landing_burn_pure_throttle_Pcontrol":
+            acts = rng.uniform(0, 1100, (n_rows, A))
+        else:
+            acts = rng.uniform(-1, 1, (n_rows, A))
+        f32 = np.arange(n_rows) % 2 == 0            # even rows: float32 actions, odd: float64
+        prev = rng.uniform(-10, 10, n_rows)
+        stoch = np.arange(n_rows) < n_stoch
+        pct = np.array([float(pcts[i % 5]) for i in range(n_rows)])
+        sigma = np.stack([0.5 + (2.25 - 0.5) * rng.random(n_rows), 1.25 + (2.0 - 1.25) * rng.random(n_rows)], 1)
+        filt_in = rng.standard_normal((n_rows, 4))
+        normals = rng.standard_normal((n_rows, 8))
+        res, inf, filt_out, gust, used = [], [], [], [], []
+        for i in range(n_rows):
+            st = [np.float64(v) for v in S[i]]
+            a = acts[i].astype(np.float32) if f32[i] else acts[i].astype(np.float64)
+            with injected_noise(normals[i], list(sigma[i])) as cnt, contextlib.redirect_stdout(io.StringIO()):
+                wg = WindModel(0.1, stochastic_wind=bool(stoch[i]), given_percentile=pcts[i % 5])
+                vk = wg.von_karman_generator_class
+                assert (vk.sigma_u, vk.sigma_v) == tuple(sigma[i]) and cnt["u"] == 2
+                vk.u_filter.state = filt_in[i, :2].copy()
+                vk.v_filter.state = filt_in[i, 2:].copy()
+                if phase == "flip_over_boostbackburn":
+                    g = np.array([prev[i]], dtype=np.float32 if f32[i] else np.float64)
+                    s2, info = fn(st, a, g, wind_generator=wg)
+                else:
+                    s2, info = fn(st, a, wind_generator=wg)
+            in_band = S[i, 1] < 15000.0
+            assert (cnt["n"] > 0) if (in_band and stoch[i]) else (cnt["n"] == 0), (tag, i, cnt["n"])
+            used.append(cnt["n"])
+            res.append([float(v) for v in s2])
+            filt_out.append(np.concatenate([vk.u_filter.state, vk.v_filter.state]))
+            gust.append([float(wg.vx_vals[-1]), float(wg.uy_vals[-1])])
+            acc, mom, ai = info["acceleration_dict"], info["moment_dict"], info["action_info"]
+            inf.append([float(acc["acceleration_x_component_wind"]), float(acc["acceleration_y_component_wind"]),
+                        float(mom["M_wind_z"]), float(info["mass_flow"]), info["air_density"], info["mach_number"],
+                        info["CL"], info["CD"], float(np.asarray(ai.get("gimbal_angle_deg", 0.0)).ravel()[0]),
+                        float(info["d_cp_cg"])])
+        out[f"{tag}_state_in"] = S
+        out[f"{tag}_action"] = acts
+        out[f"{tag}_f32"] = f32
+        out[f"{tag}_prev"] = prev
+        out[f"{tag}_stoch"] = stoch
+        out[f"{tag}_percentile"] = pct
+        out[f"{tag}_sigma"] = sigma
+        out[f"{tag}_filt_in"] = filt_in
+        out[f"{tag}_normals"] = normals
+        out[f"{tag}_n_normals"] = np.array(used)
+        out[f"{tag}_state_out"] = np.array(res)
+        out[f"{tag}_filt_out"] = np.array(filt_out)
+        out[f"{tag}_gust"] = np.array(gust)
+        out[f"{tag}_info"] = np.array(inf)
+    out["info_names"] = np.array(WIND_INFO)
+    # (b) windy RL-wrapper episodes: the second spec of phases() (seed, scale)
+    max_steps = 300
+    for tag, phase, A, seed, scale in (("pc", "landing_burn_pure_throttle_Pcontrol", 1, 34, 0.2),
+                                       ("ba", "ballistic_arc_descent", 1, 36, 0.1), ("sub", "subsonic", 2, 38, 0.05),
+                                       ("sup", "supersonic", 2, 40, 0.05)):
+        r = np.random.default_rng(seed)
+        acts = (r.uniform(-1, 1, (2500, A)) * scale).astype(np.float32)
+        if phase == "landing_burn_pure_throttle_Pcontrol":
+            acts = r.uniform(-1, 1, (2500, A)).astype(np.float32) * np.float32(scale)
+        if phase == "subsonic":      # the ascent needs throttle to leave the pad
+            acts[:, 1] = np.clip(acts[:, 1] + np.float32(0.9), -1, 1)
+        rng = np.random.default_rng(500 + seed)
+        normals = rng.standard_normal(max_steps * 8)
+        uniforms = [0.5 + (2.25 - 0.5) * rng.random(), 1.25 + (2.0 - 1.25) * rng.random()]
+        cum = []
+        with injected_noise(normals, uniforms) as cnt, contextlib.redirect_stdout(io.StringIO()):
+            env = rl_env_cls(flight_phase=phase, enable_wind=True, stochastic_wind=True,
+                             horiontal_wind_percentile=50, trajectory_length=100, discount_factor=0.99)
+            cnt["n"] = 0; cnt["u"] = 0
+            # reset() draws the per-episode sigmas (VKDisturbanceGenerator._new_filters)
+
+            def step(e, a):
+                res = e.step(a)
+                cum.append(cnt["n"])
+                return res
+            ep = run_episode(env, acts, max_steps, step)
+            vk = env.env.wind_generator.von_karman_generator_class
+            su, sv = vk.sigma_u, vk.sigma_v
+            used = cnt["n"]
+        assert (su, sv) == tuple(uniforms), tag
+        for key, v in ep.items():
+            out[f"ep_{tag}_{key}"] = v
+        out[f"ep_{tag}_actions"] = acts[:len(ep["reward"])]
+        out[f"ep_{tag}_normals"] = normals[:used]
+        out[f"ep_{tag}_sigma"] = np.array([su, sv])
+        out[f"ep_{tag}_n_normals_cum"] = np.array(cum)
+    save("ref_phases_wind.npz", **out)
+    size = os.path.getsize(os.path.join(HERE, "ref_phases_wind.npz"))
+    assert size <= os.path.getsize(os.path.join(HERE, "ref_phases.npz")), size
+
+
 def wind_profiles_ref():
     """HorizontalWindSpeed.compile_horizontal_fixed_wind for every percentile the envs use
     (WindModel: float(np.random.randint(50, 99)); the wrappers' horiontal_wind_percentile, an
@@ -464,6 +619,7 @@ def main():
     print("wind episodes", file=sys.stderr); wind_episodes(rl_env_cls)
     print("PSO objective", file=sys.stderr); pso_objective(import_reference.pso_wrapped_env)
     print("other phases", file=sys.stderr); recorded_phases(); phases(rp, rl_env_cls)
+    print("other phases with wind", file=sys.stderr); phases_wind(rp, rl_env_cls)
     print("wind profiles", file=sys.stderr); wind_profiles_ref()
 
 
@@ -477,5 +633,8 @@ if __name__ == "__main__":
         recorded_phases()
         rp, _, _, rl_env_cls, _ = import_reference()
         phases(rp, rl_env_cls)
+    elif len(sys.argv) > 1 and sys.argv[1] == "phases_wind":     # only the windy other-phases fixture
+        rp, _, _, rl_env_cls, _ = import_reference()
+        phases_wind(rp, rl_env_cls)
     else:
         main()

@@ -31,8 +31,8 @@ def snapshot(env, it):
     ep, ts, tid = env.episode_counters()
     out = dict(s=env.state[it], vprev=vp[it], ring=ring[it], len=ln[it], head=hd[it], filt=f[it], sig=sg[it],
                prof=pr[it] - 50, ep=ep[it], ts=ts[it], tid=tid[it])
-    if env.action_dim == 4:
-        out["act"] = env.actuators[it]
+    if env.action_dim == 4 or getattr(env, "flight_phase", None) == "flip_over_boostbackburn":
+        out["act"] = env.actuators[it]      # landing_burn's three memories; the flip-over's gimbal memory
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
@@ -63,6 +63,12 @@ def shadow_run(oracle_mod, env, actions, idx, phase, rtd, seed, tilt, fixed_prof
     outputs of the whole batch (for the fused-launch identity check)."""
     L = oracle_mod.lib()
     P = oracle_mod.params()
+    cfg = getattr(env, "cfg", None)
+    if cfg is not None and cfg.discount_factor > 0 and cfg.trajectory_length > 0 and \
+            (cfg.discount_factor, cfg.trajectory_length) != (P.rl_discount, P.rl_traj_len):
+        # the RL rewards of the phases that use them (rtd_rl.py) take the handle's values
+        P = type(P).from_buffer_copy(P)
+        P.rl_discount, P.rl_traj_len = cfg.discount_factor, cfg.trajectory_length
     it = torch.as_tensor(idx, device=env.device)
     T = actions.shape[0]
     o = oracle_mod.OrcOut()
