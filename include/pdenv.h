@@ -714,6 +714,48 @@ pd_status pd_sac_actor_grad(int64_t batch, int32_t state_dim, int32_t action_dim
                             float* eps_out, float* dq_da, float* dheads_out, float* actor_loss, float* alpha_loss,
                             float* log_alpha_grad, float* sumsq_partials, int32_t* n_partials, void* scratch,
                             size_t scratch_bytes, void* stream);
+/* pd_sac_learning_stats: steps 9 and 10 of SACPyTorch.update, _track_learning_stats
+ * (sac_pytorch.py:553-634), as ONE launch (csrc/pdsacstats.hip; additive exports, ABI 11).  No env
+ * handle: device pointers, the current HIP device, no host synchronisation, nothing read back -- the
+ * reference makes six device-to-host copies, four .item() calls and about thirty NumPy reductions.
+ * out_row [PD_SAC_N_STATS] binary64 receives one row of learning_stats in the reference's key order
+ * (sac_pytorch.py:346-397; pd_sac_stat_name(column) returns the key, NULL outside [0, PD_SAC_N_STATS)):
+ *   0      step
+ *   1-5    state_{mean,min,max,std,kurtosis}    6-10  action_...    11-15  reward_...
+ *   16-19  critic_loss, actor_loss, alpha_loss, alpha_value
+ *   20-23  q_value_{mean,min,max,std}    24-27  log_prob_...    28-31  target_q_...
+ *   32-34  per_beta, per_mean_weight, per_max_priority
+ *   35-36  actor_grad_norm, critic_grad_norm
+ *  rows    : [batch][width] state | action | reward | ... (a buffer's sampled rows), width >= state_dim
+ *            + action_dim + 1; q [batch][2] (the actor step's Q1 | Q2: the statistic is over
+ *            fminf(q1, q2)); target_q, log_prob [batch]; weights [batch] or NULL (a uniform buffer)
+ *  series  : each state dimension over the batch (state_dim series), all batch x action_dim action
+ *            values as one, the reward column, fminf(q1, q2), target_q, log_prob, weights
+ *  mean, min, max as np.mean / np.min / np.max; std the population standard deviation (np.std, ddof
+ *  0); kurtosis scipy.stats.kurtosis's default (Fisher, biased): m4 / m2^2 - 3 with central moments
+ *  divided by n, 0 / 0 = NaN for a constant series.  The five state_* columns are the plain mean over
+ *  the state dimensions (ascending) of the per-dimension statistic (:566-583).  A NaN anywhere in a
+ *  series makes all that series' statistics NaN, min and max included (NumPy's behaviour).
+ *  Arithmetic: every float32 is widened to binary64, all sums are binary64 and two-pass (the mean,
+ *  then the central moments about it) in an order fixed by the shape alone; no atomics: the same
+ *  inputs give the same bytes on every call.  batch == 1: std 0, kurtosis NaN.
+ *  scalars : critic_loss, actor_loss, alpha_loss, max_priority, actor_grad_norm, critic_grad_norm are
+ *            device scalars widened exactly; each may be NULL, its column is then NaN.
+ *            alpha_value = expf(*log_alpha) (pd_sac_td_target's expf).  per_mean_weight is NaN
+ *            without weights, and per_beta too; otherwise per_beta and step are stored as given
+ *            (step as a double: exact below 2^53).
+ * Only out_row is written.  PD_ERR_INVALID: batch < 1, state_dim < 1, action_dim < 1, width <
+ * state_dim + action_dim + 1, a NULL rows / q / target_q / log_prob / log_alpha / out_row;
+ * PD_ERR_UNSUPPORTED: state_dim > 16 or action_dim > 8 (the SAC kernels' domain), batch > 65536; all
+ * before any launch. */
+#define PD_SAC_N_STATS 37
+const char* pd_sac_stat_name(int32_t column);
+pd_status pd_sac_learning_stats(int64_t batch, int32_t state_dim, int32_t action_dim, const float* rows, int32_t width,
+                                const float* q, const float* target_q, const float* log_prob, const float* weights,
+                                const float* critic_loss, const float* actor_loss, const float* alpha_loss,
+                                const float* log_alpha, const float* max_priority, const float* actor_grad_norm,
+                                const float* critic_grad_norm, double per_beta, int64_t step, double* out_row,
+                                void* stream);
 /* Insert the aero neighbourhoods solved on device and still queued into the handle's tables
  * (one tiny kernel; a no-op when nothing is queued).  Since ABI 10 every step launch (pd_step,
  * pd_step_n, pd_step_sac*, pd_rollout) inserts the neighbourhoods it solved itself, by its last

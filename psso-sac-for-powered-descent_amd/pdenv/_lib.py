@@ -105,10 +105,12 @@ EXPORTS = ["pd_abi_version", "pd_sizeof_params", "pd_sizeof_config", "pd_last_er
            "pd_rollout_sac", "pd_atm_table_lds", "pd_wind_slopes", "pd_collect_sac", "pd_per_sample_scratch_bytes",
            "pd_per_sample", "pd_per_update", "pd_sac_critic", "pd_sac_td_target",
            "pd_sac_critic_grad_scratch_bytes", "pd_sac_critic_grad", "pd_adam_step", "pd_sac_critic_dinput",
-           "pd_sac_actor_grad_scratch_bytes", "pd_sac_actor_grad"]
+           "pd_sac_actor_grad_scratch_bytes", "pd_sac_actor_grad", "pd_sac_stat_name", "pd_sac_learning_stats"]
 SAC_LOSS_L2, SAC_LOSS_L1 = 0, 1   # PD_SAC_LOSS_*
 ADAM_MAX_TENSORS = 64             # PD_ADAM_MAX_TENSORS
 PER_MAX_BATCH = 1024              # PD_PER_MAX_BATCH
+SAC_N_STATS = 37                  # PD_SAC_N_STATS
+SAC_STATS_MAX_BATCH = 65536       # pd_sac_learning_stats: PD_ERR_UNSUPPORTED above
 ABI_VERSION = 11
 
 _lib = None
@@ -176,6 +178,10 @@ def load(path=None):
                                     F32, U64, U64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(I32), vp,
                                     C.c_size_t, vp]
     L.pd_sac_actor_grad.restype = C.c_int
+    L.pd_sac_stat_name.argtypes = [I32]
+    L.pd_sac_stat_name.restype = C.c_char_p
+    L.pd_sac_learning_stats.argtypes = [I64, I32, I32, vp, I32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, D, I64, vp, vp]
+    L.pd_sac_learning_stats.restype = C.c_int
     L.pd_set_tuning.argtypes = [vp, P(PdTuning)]
     L.pd_get_tuning.argtypes = [vp, P(PdTuning)]
     L.pd_rollout.argtypes = [vp, vp, I32, vp, vp]

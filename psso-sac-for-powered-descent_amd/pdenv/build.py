@@ -6,7 +6,7 @@ collection units, pd_collect_sac: each its own object, so they build next to the
 handle and C ABI (pdenv.hip) and the host table builder (pd_tables.hip: host code only, with the
 same flags, on which the tables' bits depend) -- and the PSO kernels (pdpso.hip), the SAC actor
 (pdsac.hip), the prioritized-replay kernels (pdper.hip), the SAC critic and TD-target kernels (pdsactd.hip) and the SAC critic update's
-(pdsacupd.hip) and the SAC actor update's (pdsacact.hip), then linked into one shared library.  Objects are rebuilt when any source is newer
+(pdsacupd.hip), the SAC actor update's (pdsacact.hip) and the learning-statistics kernel (pdsacstats.hip), then linked into one shared library.  Objects are rebuilt when any source is newer
 than them."""
 import concurrent.futures as cf
 import os
@@ -38,7 +38,7 @@ KSTEP_FLAGS = {(0, 0, 1): ["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"]
 
 def units():
     """(object path, source, defines) of every translation unit."""
-    u = [(os.path.join(OBJ, f"{n}.o"), f"{n}.hip", []) for n in HOST_UNITS + ("pdpso", "pdsac", "pdper", "pdsactd", "pdsacupd", "pdsacact")]
+    u = [(os.path.join(OBJ, f"{n}.o"), f"{n}.hip", []) for n in HOST_UNITS + ("pdpso", "pdsac", "pdper", "pdsactd", "pdsacupd", "pdsacact", "pdsacstats")]
     for r, ph, w in KSTEP:
         u.append((os.path.join(OBJ, f"kstep_r{r}_p{ph}_w{w}.o"), "kstep.hip",
                   [f"-DPD_KR={r}", f"-DPD_KPH={ph}", f"-DPD_KW={w}"] + KSTEP_FLAGS.get((r, ph, w), [])))

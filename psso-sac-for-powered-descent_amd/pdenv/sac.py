@@ -1122,17 +1122,240 @@ class ActorUpdate:
         return log_prob
 
 
-def sac_update(buffer, td_target, critic_update, actor_update, batch_size):
-    """One learner update in the order of SACPyTorch.update (sac_pytorch.py:411-531) on a prioritized
-    buffer: sample, TdTarget, CriticUpdate, ActorUpdate, update_priorities.  With a
-    KernelPrioritizedReplayBuffer and the three objects on their kernel paths this is a fixed sequence
-    of launches on device pointers: nothing is read back and nothing is returned."""
-    _, _, _, _, _, weights, indices = buffer.sample(batch_size)
+STAT_NAMES = ("step",
+              "state_mean", "state_min", "state_max", "state_std", "state_kurtosis",
+              "action_mean", "action_min", "action_max", "action_std", "action_kurtosis",
+              "reward_mean", "reward_min", "reward_max", "reward_std", "reward_kurtosis",
+              "critic_loss", "actor_loss", "alpha_loss", "alpha_value",
+              "q_value_mean", "q_value_min", "q_value_max", "q_value_std",
+              "log_prob_mean", "log_prob_min", "log_prob_max", "log_prob_std",
+              "target_q_mean", "target_q_min", "target_q_max", "target_q_std",
+              "per_beta", "per_mean_weight", "per_max_priority",
+              "actor_grad_norm", "critic_grad_norm")      # pd_sac_stat_name, sac_pytorch.py:346-397
+_PER_STATS = STAT_NAMES[32:35]
+_GRAD_STATS = STAT_NAMES[35:37]
+assert len(STAT_NAMES) == L.SAC_N_STATS
+
+
+class LearningStats:
+    """The reference's learning_stats (sac_pytorch.py:346-397) and _track_learning_stats (:553-634) on
+    the device: a [capacity, 37] float64 ring of rows in the reference's key order (STAT_NAMES), each
+    written by ONE pd_sac_learning_stats launch from the tensors a learner update leaves behind --
+    nothing is read back until the ring is full, or flush(), to_dict(), save_csv() or a read of
+    .columns / .rows asks for it, and then the filled rows come over in one copy.
+
+    record(rows, td_target_out, critic_update, actor_update, log_prob, weights, buffer): rows the
+    sampled [B, W] rows (buffer.last_rows), td_target_out TdTarget's [B, 1], log_prob ActorUpdate's
+    return value, weights [B, 1] or None; it reads critic_update.critic_loss / .grad_norm,
+    actor_update.q / .actor_loss / .alpha_loss / .grad_norm / .log_alpha and, where the buffer has
+    them, buffer.max_prio_dev and buffer.beta.  The `step` column is the object's own counter (.step,
+    0 at first, as the reference's self.updates).  A column whose input is missing is NaN.
+
+    kernel=None (default): the kernel where the inputs are contiguous float32 device tensors inside its
+    domain (S <= 16, A <= 8, B <= 65536), else the torch path; kernel=False: always the torch path --
+    the same 37 numbers by float64 torch reductions on the device tensors, stacked into the row
+    without an .item(); kernel=True: the kernel or an error.
+
+    to_dict() -> {name: list} in column order, without the PER keys and the grad-norm keys when they
+    were never given (the reference has them only under use_per / clip_gradients).  save_csv(path)
+    appends the rows not yet saved, with a header only when the file does not exist
+    (save_learning_stats, sac_pytorch.py:636-684)."""
+
+    def __init__(self, state_dim, action_dim, device, capacity=1024, kernel=None):
+        self.state_dim, self.action_dim = int(state_dim), int(action_dim)
+        self.device = torch.device(device)
+        self.capacity = max(1, int(capacity))
+        self.kernel = kernel
+        self.buf = torch.zeros(self.capacity, L.SAC_N_STATS, dtype=torch.float64, device=self.device)
+        self.step = 0                 # the next row's `step`
+        self.n = 0                    # rows recorded
+        self.last_kernel = None       # whether the last record() went through the kernel
+        self._flushed = 0             # rows copied to the host
+        self._saved = 0               # rows written by save_csv
+        self._host = []               # [k, 37] arrays, in order
+        self.has_per = self.has_grad_norms = False
+        self.lib = None
+
+    # ---- recording
+    def _kernel_ok(self, B, tensors, scalars):
+        if not (self.device.type == "cuda" and 1 <= B <= L.SAC_STATS_MAX_BATCH and self.state_dim <= 16
+                and self.action_dim <= 8):
+            return False
+        for t, numel in tensors:
+            if t is not None and not (t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == numel):
+                return False
+        return all(t is None or (t.dtype == torch.float32 and t.is_cuda and t.numel() == 1) for t in scalars)
+
+    @staticmethod
+    def _series(x):
+        """[5, k] mean, min, max, std (ddof 0), kurtosis (Fisher, biased) of the k columns of x [n, k]
+        in binary64, two-pass; torch's min and max give NaN for a column that holds one."""
+        n = x.shape[0]
+        mean = x.sum(0) / n
+        d2 = (x - mean) ** 2
+        m2, m4 = d2.sum(0) / n, (d2 * d2).sum(0) / n
+        return torch.stack([mean, x.min(0).values, x.max(0).values, m2.sqrt(), m4 / (m2 * m2) - 3.0])
+
+    @torch.no_grad()
+    def _torch_row(self, rows, q, target_q, log_prob, weights, scalars, log_alpha, per_beta, out):
+        S, A, f64 = self.state_dim, self.action_dim, torch.float64
+        B = int(rows.shape[0])
+        dev = rows.device
+
+        def const(v):
+            return torch.full((1,), float(v), dtype=f64, device=dev)
+
+        def scalar(t):
+            return const("nan") if t is None else t.detach().reshape(-1)[:1].to(f64)
+
+        def flat(t, cols=4):
+            return self._series(t.detach().reshape(B, -1)[:, :1].to(f64))[:cols, 0]
+
+        closs, aloss, alloss, maxp, agn, cgn = scalars
+        per_dim = self._series(rows[:, :S].to(f64))
+        state = per_dim[:, 0]
+        for d in range(1, S):         # (ascending, as the kernel adds them: torch's sum has its own order)
+            state = state + per_dim[:, d]
+        state = state / S
+        action = self._series(rows[:, S:S + A].to(f64).reshape(-1, 1))[:, 0]
+        qq = q.detach().reshape(B, 2)
+        qmin = torch.fmin(qq[:, 0], qq[:, 1])
+        alpha = log_alpha.detach().reshape(-1)[:1].float().exp().to(f64)
+        have_w = weights is not None
+        out.copy_(torch.cat([
+            const(self.step), state, action, flat(rows[:, S + A:S + A + 1], 5),
+            scalar(closs), scalar(aloss), scalar(alloss), alpha,
+            flat(qmin), flat(log_prob), flat(target_q),
+            const(per_beta if have_w else "nan"),
+            weights.detach().reshape(-1).to(f64).sum().reshape(1) / B if have_w else const("nan"), scalar(maxp),
+            scalar(agn), scalar(cgn)]))
+
+    def record(self, rows, td_target_out, critic_update, actor_update, log_prob, weights=None, buffer=None):
+        B, S, A = int(rows.shape[0]), self.state_dim, self.action_dim
+        q, log_alpha = actor_update.q, actor_update.log_alpha
+        scalars = (critic_update.critic_loss, actor_update.actor_loss, actor_update.alpha_loss,
+                   getattr(buffer, "max_prio_dev", None) if weights is not None else None,
+                   actor_update.grad_norm, critic_update.grad_norm)
+        per_beta = float(getattr(buffer, "beta", float("nan")))
+        out = self.buf[self.n % self.capacity]
+        use = self.kernel
+        if use is None or use:
+            ok = (rows.dim() == 2 and rows.dtype == torch.float32 and rows.is_cuda and B > 0 and rows.stride(1) == 1
+                  and rows.stride(0) >= S + A + 1
+                  and self._kernel_ok(B, ((q, 2 * B), (td_target_out, B), (log_prob, B), (weights, B)),
+                                      scalars + (log_alpha,)))
+            if use and not ok:
+                raise ValueError("LearningStats(kernel=True): contiguous float32 device tensors inside "
+                                 "pd_sac_learning_stats' domain are required")
+            use = ok
+        if use:
+            if self.lib is None:
+                self.lib = L.load()
+            L.check(self.lib.pd_sac_learning_stats(
+                B, S, A, _ptr(rows), int(rows.stride(0)), _ptr(q), _ptr(td_target_out), _ptr(log_prob), _ptr(weights),
+                *[_ptr(t) for t in scalars[:3]], _ptr(log_alpha), *[_ptr(t) for t in scalars[3:]], per_beta,
+                int(self.step), _ptr(out), _stream(rows.device)))
+        else:
+            self._torch_row(rows, q, td_target_out, log_prob, weights, scalars, log_alpha, per_beta, out)
+        self.last_kernel = bool(use)
+        self.has_per = self.has_per or weights is not None
+        self.has_grad_norms = self.has_grad_norms or scalars[4] is not None or scalars[5] is not None
+        self.step += 1
+        self.n += 1
+        if self.n - self._flushed >= self.capacity:
+            self.flush()
+
+    # ---- reading
+    def flush(self):
+        """The rows recorded since the last flush to the host, in ONE copy (the reader's
+        synchronisation)."""
+        k = self.n - self._flushed
+        if k <= 0:
+            return
+        a = self._flushed % self.capacity
+        b = a + k
+        if b <= self.capacity:
+            part = self.buf[a:b]
+        else:                          # (wrapped: gathered on the device, still one copy)
+            part = torch.cat([self.buf[a:], self.buf[:b - self.capacity]])
+        self._host.append(part.cpu().numpy().copy())
+        self._flushed = self.n
+
+    @property
+    def rows(self):
+        """[n, 37] float64 numpy: every row recorded so far."""
+        import numpy as np
+        self.flush()
+        if len(self._host) > 1:
+            self._host = [np.concatenate(self._host)]
+        return self._host[0] if self._host else np.zeros((0, L.SAC_N_STATS))
+
+    @property
+    def columns(self):
+        """{name: [n] float64 numpy} over all 37 columns."""
+        r = self.rows
+        return {name: r[:, k] for k, name in enumerate(STAT_NAMES)}
+
+    def keys(self):
+        return [n for n in STAT_NAMES if (self.has_per or n not in _PER_STATS)
+                and (self.has_grad_norms or n not in _GRAD_STATS)]
+
+    def to_dict(self, start=0):
+        cols = self.columns
+        out = {name: cols[name][start:].tolist() for name in self.keys()}
+        out["step"] = [int(v) for v in out["step"]]
+        return out
+
+    def __len__(self):
+        return self.n
+
+    def save_csv(self, path):
+        """Append the rows not yet saved to `path`; the header only when the file does not exist.
+        Returns the number of rows written."""
+        import os
+        new = self.to_dict(start=self._saved)
+        k = len(new["step"])
+        if k == 0:
+            return 0
+        d = os.path.dirname(path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        exists = os.path.isfile(path)
+        try:
+            import pandas as pd
+        except ImportError:
+            pd = None
+        if pd is not None:
+            pd.DataFrame(new).to_csv(path, mode="a" if exists else "w", header=not exists, index=False)
+        else:
+            import csv
+            with open(path, "a" if exists else "w", newline="") as f:
+                w = csv.writer(f)
+                if not exists:
+                    w.writerow(list(new))
+                w.writerows(zip(*new.values()))
+        self._saved = self.n
+        return k
+
+
+def sac_update(buffer, td_target, critic_update, actor_update, batch_size, stats=None):
+    """One learner update in the order of SACPyTorch.update (sac_pytorch.py:411-531): sample, TdTarget,
+    CriticUpdate, ActorUpdate, update_priorities (a prioritized buffer; a uniform DeviceReplayBuffer,
+    whose sample is a 5-tuple, has no weights and no priorities) and, with `stats` (a LearningStats),
+    the update's learning_stats row (step 9) -- after update_priorities, so that it logs what the
+    reference logs: alpha after its step, the max priority after step 7, beta after the sample's
+    annealing.  With a KernelPrioritizedReplayBuffer and the objects on their kernel paths this is a
+    fixed sequence of launches on device pointers: nothing is read back and nothing is returned."""
+    batch = buffer.sample(batch_size)
+    weights, indices = (batch[5], batch[6]) if len(batch) >= 7 else (None, None)
     rows = buffer.last_rows
     target_q = td_target(rows)
     td_abs = critic_update(rows, target_q, weights)
-    actor_update(rows, weights)
-    buffer.update_priorities(indices, td_abs)
+    log_prob = actor_update(rows, weights)
+    if indices is not None:
+        buffer.update_priorities(indices, td_abs)
+    if stats is not None:
+        stats.record(rows, target_q, critic_update, actor_update, log_prob, weights, buffer)
 
 
 class SACCollector:
